@@ -9,7 +9,14 @@ all-reduce(sum) of the embedding gradient inside the timed region — issued thr
 library's own communicator (mm_allreduce_sum, include/mm_manifolds.h) and captured in the
 same hipGraph as the kernels.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line; nothing else.  --full adds what
+takes runs of its own: the phase pass and synchronised steps, the eager-path timings, per-kernel durations
+and rooflines, the shader clock, the secondary workloads and the CPU baseline (--no-prof, --no-extra and
+--no-cpu-baseline leave parts of that out).  --dump-outputs DIR writes what the last timed step computed
+(rank 0's squared distances `d2` and the embedding gradient `grad`) as DIR/<name>.npy; the inputs are
+seeded, so two builds can be compared output for output.
 
 N > 1: `python bench.py --gpus N` starts its N ranks itself (a child `torch.distributed.run`,
 started before this process touches a GPU; the child's exit code is passed on, a run that
@@ -46,9 +53,13 @@ def parse_args(argv=None):
     ap.add_argument('--steps', type=int, default=50)
     ap.add_argument('--warmup', type=int, default=10)
     ap.add_argument('--n', type=int, default=N_NODES)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-prof', action='store_true', help='no HIP-event bracketing of the kernels')
-    ap.add_argument('--no-extra', action='store_true', help='headline only (no secondary workloads)')
+    ap.add_argument('--full', action='store_true',
+                    help='also the diagnostics, secondary workloads and CPU baseline (a plain run times the headline only)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed as DIR/<name>.npy (at most 64 MB in all)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: no CPU baseline')
+    ap.add_argument('--no-prof', action='store_true', help='--full: no HIP-event bracketing of the kernels')
+    ap.add_argument('--no-extra', action='store_true', help='--full: headline only (no secondary workloads)')
     ap.add_argument('--graph', choices=['auto', 'on', 'off'], default='auto',
                     help='replay the step from a captured hipGraph (auto = on; falls back to eager launches '
                          'if capture is unavailable)')
@@ -169,6 +180,31 @@ def kernel_source_hash():
                 h.update(name.encode())
                 h.update(f.read())
     return h.hexdigest()[:16]
+
+
+DUMP_BUDGET_BYTES = 64_000_000
+
+
+def dump_outputs(dirname, arrays, seed=0):
+    """Writes each (name, tensor) as dirname/<name>.npy in its own float dtype.  If the arrays exceed the 64 MB budget, the
+    largest ones are replaced by a fixed seeded sample of their elements (same indices on every run with the same shapes)."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: v.detach() for k, v in arrays.items()}
+    total = sum(v.numel() * v.element_size() for v in arrays.values())
+    for name in sorted(arrays, key=lambda k: -arrays[k].numel()):
+        if total <= DUMP_BUDGET_BYTES:
+            break
+        v = arrays[name]
+        keep = max(1, v.numel() - (total - DUMP_BUDGET_BYTES) // v.element_size())
+        gen = torch.Generator().manual_seed(seed)
+        idx = torch.randint(v.numel(), (keep,), generator=gen).sort().values
+        arrays[name + '_sample'] = v.reshape(-1)[idx.to(v.device)]
+        del arrays[name]
+        total -= (v.numel() - keep) * v.element_size()
+    for name, v in arrays.items():
+        np.save(os.path.join(dirname, name + '.npy'), v.cpu().numpy())
 
 
 def stamped_pmc():
@@ -293,6 +329,7 @@ class PdistWorkload:
         import torch
         d2 = self.man.pdist(self.x, squared=True, rows=self.rows)
         grad, = torch.autograd.grad(d2, self.x, self.g_local)
+        self.d2 = d2       # (kept for --dump-outputs; a captured graph rewrites it on every replay)
         return grad
 
     def reduce(self, t):
@@ -426,10 +463,12 @@ class TrainStepWorkload:
 
 
 def time_workload(wl, steps, warmup, fence, use_graph, graph_collective=False, rank=0, tag='', warm_seconds=0.0,
-                  min_timed_seconds=0.0):
+                  min_timed_seconds=0.0, phase_pass=True, after_timed=None):
     """Times `steps` steps of the workload between fences.  Returns (elapsed_s, launch_mode, phases) where
     phases = per-step means, in us, of this rank's device time in the kernels and in the all-reduce and of
-    the rest of the step's wall time (host gap), from an instrumented pass after the timed region.
+    the rest of the step's wall time (host gap), from an instrumented pass after the timed region
+    (phase_pass=False: no such pass, phases holds the step count only).
+    after_timed(out), if given, is called right after the timed region with what the last timed step returned.
     min_timed_seconds > 0 (secondary workloads only — the headline times EXACTLY the steps it is asked for): the step
     count is raised until the timed region lasts that long (20 steps of a 50-us workload are one millisecond: a single
     scheduling hiccup doubles the figure); phases['steps'] is the count used."""
@@ -492,9 +531,11 @@ def time_workload(wl, steps, warmup, fence, use_graph, graph_collective=False, r
     if in_call:
         in_graph_collective = True     # (nothing to issue after the kernels, graphed or not)
 
+    last = [None]
+
     def run():
         if graph is None:
-            wl.eager_step()
+            last[0] = wl.eager_step()
             return
         graph.replay()
         if world > 1 and not in_graph_collective:
@@ -538,6 +579,10 @@ def time_workload(wl, steps, warmup, fence, use_graph, graph_collective=False, r
         run()
     fence()
     elapsed = time.perf_counter() - t0
+    if after_timed is not None:
+        after_timed(static if graph is not None else last[0])
+    if not phase_pass:
+        return elapsed, mode, {'steps': steps, '_run': run}
 
     # phase pass (not timed): events on the launch stream around the kernels and around the collective
     k2 = max(3, min(steps, 20))
@@ -651,8 +696,12 @@ def worker(args):
     wl = PdistWorkload(DIM, n, torch.float32, 0.1, world, rank, dev, comm=comm)
     # (W warm-up steps as asked, then 50 ms more of untimed steps: W = 10 steps are under a millisecond of GPU time, not
     # enough for the clocks to settle after the seconds of host-side input generation)
+    dump = None
+    if args.dump_outputs and rank == 0:
+        def dump(grad):
+            dump_outputs(args.dump_outputs, {'d2': wl.d2, 'grad': grad})
     elapsed, mode, phases = time_workload(wl, args.steps, args.warmup, fence, use_graph, graph_collective, rank,
-                                          warm_seconds=0.05)
+                                          warm_seconds=0.05, phase_pass=args.full, after_timed=dump)
     elapsed = reduce_max(elapsed, dev, world)
 
     # per-kernel durations: HIP events attached to each pair kernel's own dispatch on the launch stream
@@ -661,7 +710,8 @@ def worker(args):
     # right after the timed region; one discarded pass first (event creation, allocator warm-up).
     kern, eager_ms, eager_st_ms = {'fwd': None, 'bwd': None}, None, None
     run_step = phases.pop('_run')
-    if not args.no_prof:
+    prof = args.full and not args.no_prof
+    if prof:
         # (a) the same step through Python autograd, one synchronised step at a time: its host cost
         wl.eager_step()
         fence()
@@ -703,7 +753,7 @@ def worker(args):
         lib.call('mm_prof_enable', 0)
         kern = collect_kernel_us(lib)
     clock_mhz = None
-    if not args.no_prof:
+    if prof:
         try:
             clock_mhz = shader_clock_mhz(lib, run_step, dev)
         except Exception as exc:  # noqa: BLE001 — a diagnostic: never fails the run
@@ -733,9 +783,10 @@ def worker(args):
                        'untimed_warm_seconds': 0.05},
             'per_rank': per_rank,
             'kernel_source_hash': kernel_source_hash(),
-            # the same step measured SURVEY.md §8d's way: median of single synchronised steps (launch latency + sync inside)
-            'ms_per_step_median_synchronised': (phases.get('synchronised_step_us_median') or 0.0) / 1e3 or None,
         }
+        if args.full:
+            # the same step measured SURVEY.md §8d's way: median of single synchronised steps (launch latency + sync inside)
+            out['ms_per_step_median_synchronised'] = (phases.get('synchronised_step_us_median') or 0.0) / 1e3 or None
         if eager_ms is not None:
             # same step issued through Python autograd (host-bound); median of single synchronised steps
             out['eager_ms_per_step'] = eager_ms
@@ -744,7 +795,7 @@ def worker(args):
                                  else 'torch.autograd.Function classes')
             if eager_st_ms is not None:
                 out['eager_ms_per_step_autograd_single_thread'] = eager_st_ms
-        pmc = stamped_pmc() if (n == N_NODES and world == 1) else None
+        pmc = stamped_pmc() if (args.full and n == N_NODES and world == 1) else None
         if kern['bwd']:
             # dominant kernel: spd_pdist_bwd.  Algorithmic HBM bytes per launch: read g (4 B per pair) + node
             # factors in (2*6 floats) + accumulators out (2*6 floats) per node.
@@ -785,7 +836,7 @@ def worker(args):
 
     # ---- secondary workloads, same JSON line ----------------------------------------------------
     extra = []
-    if not args.no_extra:
+    if args.full and not args.no_extra:
         kbase, w2 = max(5, min(args.steps, 20)), max(2, min(args.warmup, 5))
         k2 = kbase   # (per workload: the count its timed region used, >= kbase — time_workload, min_timed_seconds)
         cases = []
@@ -940,7 +991,7 @@ def worker(args):
     if rank == 0:
         if extra:
             out['extra'] = extra
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(42, n)
         print(json.dumps(out), flush=True)
     if comm is not None:

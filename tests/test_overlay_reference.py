@@ -1,10 +1,12 @@
-"""INTEGRATION.md option A, executed: this package AHEAD of the maintainer's reference checkout on PYTHONPATH.
+"""INTEGRATION.md option A, executed: this package AHEAD of a maintainer's checkout of the reference on PYTHONPATH.
 
-Runs only where the reference is present (the build container; `/root/reference` does not exist on the GPU box) and in
-fresh interpreters, so the `graphembed` of this test process is not touched.  What is checked is run.py's own import
-block (run.py:15-18), the engines it selects (run.py:76-81), what `graphembed/__init__.py:1-9` of the reference imports,
-and the dotted names `parse_config` resolves for example_config.yaml (run.py:136-206) — the hot-path names must come from
-THIS package, the control plane from the checkout.  Nothing of the reference is copied: the checkout is only on the path.
+The checkout is a stand-in written by this module into a temporary directory: the reference's package layout with small
+modules of its own (the module and class names run.py, `graphembed/__init__.py` and example_config.yaml ask for), some of
+them decoys that also define names this package defines.  Everything runs in fresh interpreters, so the `graphembed` of
+this test process is not touched.  What is checked is run.py's own import block (run.py:15-18), the engines it selects
+(run.py:76-81), the sub-packages the reference's `graphembed/__init__.py` imports, and the dotted names `parse_config`
+resolves for a config (run.py:136-206) — the hot-path names must come from THIS package, the control plane from the
+checkout.
 
 tensorboard and ruamel.yaml are not in this image: `torch.utils.tensorboard` is stubbed (as SURVEY.md's Appendix B does)
 and the config is read with PyYAML — the name resolution itself is run.py's `importlib.import_module` + `getattr`.
@@ -18,10 +20,174 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, 'matrix-manifolds_amd')
-REF = '/root/reference/graphembed'
 
-pytestmark = pytest.mark.skipif(not os.path.isfile(os.path.join(REF, 'graphembed', '__init__.py')),
-                                reason='the reference checkout is only present in the build container')
+# the stand-in checkout: path under <checkout>/graphembed -> source.  No __init__.py in linalg/ (as on both real sides).
+CHECKOUT = {
+    '__init__.py': """
+        # (never executed: the package that comes first on the path owns `graphembed`)
+        from . import data, linalg, manifolds, optim, modules, objectives, train
+    """,
+    'data/__init__.py': '',
+    'data/preprocess.py': """
+        def load_graph_pdists(*a, **k):   # decoy: this package's data.load_graph_pdists must win
+            raise AssertionError('the checkout was asked')
+    """,
+    'linalg/fast.py': """
+        import torch
+
+        def symeig3x3(x):
+            return torch.linalg.eigvalsh(x)
+
+        def cholesky2x2(x):
+            return torch.linalg.cholesky(x)
+
+        def invcholesky2x2(x, ret_chol=False):
+            l = torch.linalg.cholesky(x)
+            li = torch.linalg.inv(l)
+            return (li, l) if ret_chol else li
+    """,
+    'linalg/torch_batch.py': """
+        import torch
+
+        def batch_eigvalsh(x):
+            return torch.linalg.eigvalsh(x.cpu()).to(x.device)
+    """,
+    'manifolds/__init__.py': '',
+    'manifolds/spd.py': """
+        class SymmetricPositiveDefinite:   # decoy
+            pass
+    """,
+    'manifolds/universal.py': """
+        from .base import Manifold
+
+        class Universal(Manifold):
+            pass
+    """,
+    'manifolds/orthogonal.py': """
+        from .base import Manifold
+
+        class OrthogonalGroup(Manifold):
+            pass
+
+        class SpecialOrthogonalGroup(OrthogonalGroup):
+            pass
+    """,
+    'optim/__init__.py': '',
+    'pyx/__init__.py': '',
+    'modules.py': """
+        import torch
+
+        class EmbeddingBase(torch.nn.Module):
+            pass
+
+        class ManifoldEmbedding(EmbeddingBase):   # decoy
+            pass
+
+        class BatchedObjective:                   # decoy
+            pass
+    """,
+    'objectives.py': """
+        class KLDiveregenceLoss:
+            pass
+
+        class QuotientLoss:                       # decoy
+            pass
+    """,
+    'utils.py': """
+        import threading
+
+        PLT_MUTEX = threading.Lock()
+
+        def latest_path_by_basename_numeric_order(paths):
+            return max(paths)
+
+        def check_mkdir(path):                    # decoy
+            raise AssertionError('the checkout was asked')
+    """,
+    'monitor.py': """
+        from graphembed.manifolds import Euclidean, Lorentz, SymmetricPositiveDefinite
+        from graphembed.utils import PLT_MUTEX
+
+        class ManifoldParameterMonitoring:
+            kinds = (Euclidean, Lorentz, SymmetricPositiveDefinite)
+    """,
+    'train.py': """
+        import numpy as np
+        import torch
+        from torch.utils.tensorboard import SummaryWriter
+
+        from graphembed.modules import BatchedObjective
+        from graphembed.utils import PLT_MUTEX, latest_path_by_basename_numeric_order
+
+        class TrainingEngine:
+            def __init__(self, objective):
+                assert isinstance(objective, BatchedObjective)
+                self.objective = objective
+    """,
+    'train_da.py': """
+        import numpy as np
+        import torch
+        from torch.utils.tensorboard import SummaryWriter
+
+        from graphembed.modules import BatchedObjective
+        from graphembed.train import TrainingEngine as Base
+
+        class TrainingEngine(Base):
+            pass
+    """,
+    'products/__init__.py': """
+        from .embedding import Embedding
+        from .train import TrainingEngine
+    """,
+    'products/embedding.py': """
+        from graphembed.manifolds import Universal
+        from graphembed.modules import EmbeddingBase, ManifoldParameter
+        from graphembed.monitor import ManifoldParameterMonitoring as Monitor
+
+        class Embedding(EmbeddingBase):
+            pass
+    """,
+    'products/train.py': """
+        from graphembed.train import TrainingEngine as Base
+
+        class TrainingEngine(Base):
+            pass
+    """,
+    'inference/__init__.py': """
+        from .base import Inference
+    """,
+    'inference/base.py': """
+        class Inference:
+            pass
+    """,
+}
+
+# the dotted names of a run.py config, under its `object` / `closure` keys
+EXAMPLE_CONFIG = """
+    embedding:
+      object: {name: graphembed.modules.ManifoldEmbedding}
+      manifold:
+        object: {name: graphembed.manifolds.SymmetricPositiveDefinite}
+    optimizer:
+      object: {name: graphembed.optim.RiemannianAdam}
+    loss:
+      object: {name: graphembed.objectives.KLDiveregenceLoss}
+      schedule:
+        closure: {name: graphembed.utils.latest_path_by_basename_numeric_order}
+"""
+
+
+@pytest.fixture(scope='module')
+def ref(tmp_path_factory):
+    """Directory of the stand-in checkout (the one that holds `graphembed/`)."""
+    base = tmp_path_factory.mktemp('checkout')
+    for rel, text in CHECKOUT.items():
+        path = base / 'graphembed' / rel
+        path.parent.mkdir(parents=True, exist_ok=True)
+        path.write_text(textwrap.dedent(text).lstrip())
+    (base / 'example_config.yaml').write_text(textwrap.dedent(EXAMPLE_CONFIG).lstrip())
+    return str(base)
+
 
 PRELUDE = textwrap.dedent('''
     import os, sys, types
@@ -42,16 +208,16 @@ PRELUDE = textwrap.dedent('''
 ''')
 
 
-def run(body, ours_first=True):
-    env = dict(os.environ, MM_PKG=PKG, MM_REF=REF, PYTHONDONTWRITEBYTECODE='1')
-    env['PYTHONPATH'] = os.pathsep.join([PKG, REF] if ours_first else [REF, PKG])
+def run(body, ref, ours_first=True):
+    env = dict(os.environ, MM_PKG=PKG, MM_REF=ref, PYTHONDONTWRITEBYTECODE='1')
+    env['PYTHONPATH'] = os.pathsep.join([PKG, ref] if ours_first else [ref, PKG])
     r = subprocess.run([sys.executable, '-c', PRELUDE + textwrap.dedent(body)], env=env, capture_output=True, text=True,
-                       timeout=300, cwd='/tmp')
+                       timeout=300, cwd=os.path.dirname(ref))
     assert r.returncode == 0, r.stdout + r.stderr
     return r.stdout
 
 
-def test_run_py_import_block_resolves_across_both_packages():
+def test_run_py_import_block_resolves_across_both_packages(ref):
     out = run('''
         from graphembed.data import load_graph_pdists, GraphDataset                      # run.py:15
         from graphembed.products.embedding import Embedding as ProductManifoldEmbedding   # run.py:16
@@ -89,15 +255,15 @@ def test_run_py_import_block_resolves_across_both_packages():
         # the reference's Universal manifold subclasses THIS package's Manifold (one class hierarchy, not two)
         assert issubclass(manifolds.Universal, manifolds.Manifold) and origin(manifolds.Manifold) == 'ours'
         print('ok')
-    ''')
+    ''', ref)
     assert out.strip().endswith('ok')
 
 
-def test_attribute_misses_stay_attribute_errors():
+def test_attribute_misses_stay_attribute_errors(ref):
     """An attribute MISS on the overlaid package must not import (and fail in) checkout modules that merely mention the
     name: `hasattr(graphembed, 'torch')` used to raise ModuleNotFoundError('tensorboard') out of the reference's train.py
     (advisor, round 4).  Run WITHOUT the tensorboard stub of the other tests."""
-    env = dict(os.environ, MM_PKG=PKG, MM_REF=REF, PYTHONDONTWRITEBYTECODE='1', PYTHONPATH=os.pathsep.join([PKG, REF]))
+    env = dict(os.environ, MM_PKG=PKG, MM_REF=ref, PYTHONDONTWRITEBYTECODE='1', PYTHONPATH=os.pathsep.join([PKG, ref]))
     code = textwrap.dedent('''
         import sys
         import graphembed, graphembed._overlay as o
@@ -121,11 +287,11 @@ def test_attribute_misses_stay_attribute_errors():
         assert o.later_packages() is not o.later_packages() and o._later_cache      # cached scan, fresh list
         print('ok')
     ''')
-    r = subprocess.run([sys.executable, '-c', code], env=env, capture_output=True, text=True, timeout=300, cwd='/tmp')
+    r = subprocess.run([sys.executable, '-c', code], env=env, capture_output=True, text=True, timeout=300, cwd=os.path.dirname(ref))
     assert r.returncode == 0 and r.stdout.strip().endswith('ok'), r.stdout + r.stderr
 
 
-def test_linalg_fast_hands_cpu_tensors_to_the_checkout():
+def test_linalg_fast_hands_cpu_tensors_to_the_checkout(ref):
     """graphembed.linalg.fast of this package shadows the checkout's: its CPU callers (monitor.py, tests/test_linalg.py) get
     the checkout's own functions for CPU tensors (advisor, round 4); GPU tensors stay on the kernels."""
     out = run('''
@@ -146,11 +312,11 @@ def test_linalg_fast_hands_cpu_tensors_to_the_checkout():
         assert torch.allclose(li @ lc, torch.eye(2, dtype=torch.float64).expand(7, 2, 2), atol=1e-6)
         assert origin(fast._reference_fast()) == 'reference'
         print('ok')
-    ''')
+    ''', ref)
     assert out.strip().endswith('ok')
 
 
-def test_example_config_names_resolve_like_parse_config():
+def test_example_config_names_resolve_like_parse_config(ref):
     out = run('''
         import importlib, yaml
         cfg = yaml.safe_load(open(os.path.join(REF, 'example_config.yaml')))
@@ -177,11 +343,11 @@ def test_example_config_names_resolve_like_parse_config():
         assert got['graphembed.optim.RiemannianAdam'] == 'ours'
         assert got['graphembed.objectives.KLDiveregenceLoss'] == 'reference'   # (not on the hot path: SURVEY.md section 2)
         print('ok')
-    ''')
+    ''', ref)
     assert out.strip().endswith('ok')
 
 
-def test_without_a_checkout_behind_it_the_package_is_unchanged():
+def test_without_a_checkout_behind_it_the_package_is_unchanged(tmp_path):
     env = dict(os.environ, PYTHONPATH=PKG, PYTHONDONTWRITEBYTECODE='1')
     code = textwrap.dedent('''
         import graphembed, graphembed._overlay as o
@@ -191,5 +357,5 @@ def test_without_a_checkout_behind_it_the_package_is_unchanged():
         except ModuleNotFoundError:
             print('ok')
     ''')
-    r = subprocess.run([sys.executable, '-c', code], env=env, capture_output=True, text=True, timeout=300, cwd='/tmp')
+    r = subprocess.run([sys.executable, '-c', code], env=env, capture_output=True, text=True, timeout=300, cwd=tmp_path)
     assert r.returncode == 0 and r.stdout.strip() == 'ok', r.stdout + r.stderr

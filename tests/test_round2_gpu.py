@@ -99,7 +99,7 @@ def test_bench_two_ranks_on_one_gpu_gloo():
     for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK'):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '10', '--warmup', '3',
-                        '--no-cpu-baseline', '--launch-timeout', '600'], env=env, capture_output=True, text=True,
+                        '--full', '--no-cpu-baseline', '--launch-timeout', '600'], env=env, capture_output=True, text=True,
                        timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
@@ -127,6 +127,44 @@ def test_bench_rank_watchdog_exits_nonzero():
                        text=True, timeout=300)
     assert r.returncode == 3, (r.returncode, r.stderr[-1000:])
     assert 'rank-timeout' in r.stderr
+
+
+def test_bench_plain_run_dumps_the_last_timed_step(tmp_path):
+    """A plain `bench.py` run times the headline only, exactly --steps steps, and --dump-outputs writes what its last timed
+    step computed: the squared distances and the embedding gradient of the seeded workload, as the oracle port has them."""
+    import importlib.util
+    from oracle import ref_port
+    env = dict(os.environ)
+    for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK'):
+        env.pop(k, None)
+    n = 600
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '7', '--warmup', '2', '--n', str(n),
+                        '--dump-outputs', str(tmp_path)], env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
+    assert len(lines) == 1, r.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out['steps'] == 7 and out['warmup'] == 2 and out['ms_per_step'] > 0 and out['value'] > 0
+    assert out['unit'] == 'pairs/s' and out['higher_is_better'] is True and out['dtype'] == 'f32'
+    for key in ('extra', 'cpu_baseline', 'roofline', 'eager_ms_per_step', 'ms_per_step_median_synchronised'):
+        assert key not in out, key
+    d2, grad = np.load(tmp_path / 'd2.npy'), np.load(tmp_path / 'grad.npy')
+    assert d2.dtype == np.float32 and d2.shape == (n * (n - 1) // 2,)
+    assert grad.dtype == np.float32 and grad.shape == (n, 3, 3)
+
+    spec = importlib.util.spec_from_file_location('bench_dump', os.path.join(ROOT, 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    x, g = bench.synthetic_spd(n, 3, 42, 'cpu')          # the inputs PdistWorkload builds (seed 42, fp32)
+    xr = x.double().requires_grad_()
+    ref = ref_port.SPD(3).pdist(xr, squared=True)
+    ref_g, = torch.autograd.grad((ref * g.double()).sum(), xr)
+    ref_g = 0.5 * (ref_g + ref_g.transpose(1, 2))
+    ref = ref.detach().numpy()
+    err = np.abs(d2.astype(np.float64) - ref)
+    assert (err <= 1e-6 + 2e-5 * np.abs(ref)).all(), err.max()
+    gerr = np.abs(grad.astype(np.float64) - ref_g.numpy()).max() / np.abs(ref_g.numpy()).max()
+    assert gerr <= 2e-5, gerr
 
 
 # A fixed-seed slice of every randomised campaign (the campaigns themselves, thousands of cases each, are run by

@@ -219,6 +219,34 @@ def test_pmc_stamp_goes_stale_with_the_sources(tmp_path, monkeypatch):
     assert bench.stamped_pmc() is None
 
 
+def test_bench_dump_outputs_keeps_to_the_budget(tmp_path, monkeypatch):
+    """--dump-outputs writes each array as <name>.npy in its own float dtype; past the size budget the largest arrays are
+    replaced by a fixed seeded sample (the same on every run), and a plain run is the default."""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location('bench_mod3', os.path.join(ROOT, 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    args = bench.parse_args(['--steps', '3'])
+    assert args.full is False and args.dump_outputs is None and args.steps == 3
+    assert bench.parse_args(['--full', '--dump-outputs', 'd']).dump_outputs == 'd'
+    big = torch.arange(100_000, dtype=torch.float32)
+    small = torch.linspace(0, 1, 90, dtype=torch.float64).reshape(10, 3, 3)
+    bench.dump_outputs(str(tmp_path / 'a'), {'d2': big, 'grad': small})
+    assert np.array_equal(np.load(tmp_path / 'a' / 'd2.npy'), big.numpy())
+    got = np.load(tmp_path / 'a' / 'grad.npy')
+    assert got.dtype == np.float64 and np.array_equal(got, small.numpy())
+    monkeypatch.setattr(bench, 'DUMP_BUDGET_BYTES', 40_000)
+    for sub in ('b', 'c'):
+        bench.dump_outputs(str(tmp_path / sub), {'d2': big, 'grad': small})
+    files = sorted(os.listdir(tmp_path / 'b'))
+    assert files == ['d2_sample.npy', 'grad.npy']
+    sample = np.load(tmp_path / 'b' / 'd2_sample.npy')
+    assert sample.dtype == np.float32 and sample.nbytes + small.numel() * 8 <= 40_000
+    assert np.all(np.diff(sample) >= 0) and np.isin(sample, big.numpy()).all()
+    assert np.array_equal(sample, np.load(tmp_path / 'c' / 'd2_sample.npy'))
+
+
 def test_spd_entry_points_validate_arguments_before_touching_the_gpu():
     """Argument errors come back as MM_ERR_ARG from the C ABI without a launch (no GPU needed): null pointers, row
     ranges outside [0, n], more nodes than the 32-bit table offsets address (include/mm_manifolds.h, mm_spd_pdist_fwd)."""

@@ -7,7 +7,7 @@
 #   3. per-case kernel stats + PMC: fp64, mid-training spread, SPD(4) sizes of BASELINE config 5 (init and mid-training),
 #      SPD(6) / SPD(9), Lorentz(11) with the MFMA counters, the mixed-manifold pair kernel at n = 1025 and n = 5000
 #   4. the warm-regime shader clock from in-kernel stamps (lib/variants/libmm_stamp.so, if built)
-#   5. a default `python3 bench.py` run, tools/bench_configs.py, tools/shard_kernel_times.py, the eager-path host profile
+#   5. a `python3 bench.py --full` run, tools/bench_configs.py, tools/shard_kernel_times.py, the eager-path host profile
 TAG=${1:-r06}
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 mkdir -p $OUT
@@ -15,8 +15,9 @@ cd $GRAFT_REPO_ROOT
 timeout 1500 python -m pytest tests -m gpu -x -q > $OUT/pytest_gpu.log 2>&1
 echo "pytest rc=$?"; tail -3 $OUT/pytest_gpu.log
 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -2
+REPO=$(pwd)
 cd /tmp && export TMPDIR=/tmp
-B="python3 /root/repo/bench.py --no-cpu-baseline --no-extra"
+B="python3 $REPO/bench.py --full --no-cpu-baseline --no-extra"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bench_stats -o s -- $B --steps 20 --warmup 5 > $OUT/bench_stats.log 2>&1
 P="$B --steps 3 --warmup 1 --no-prof"
 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_ANY SQ_WAIT_ANY SQ_WAIT_INST_ANY --output-format csv -d $OUT/bench_pmc_sq -o p -- $P > /dev/null 2>&1
@@ -50,7 +51,7 @@ for N in 1025 5000; do
   rocprofv3 --pmc WRITE_SIZE TCC_EA0_ATOMIC_sum --output-format csv -d $OUT/case_product_${N}_pmc_write -o p -- $C product $N f32 3 > /dev/null 2>&1
 done
 cd $GRAFT_REPO_ROOT
-python3 tools/pmc_stamp.py gpurun_out/$TAG/bench_pmc_sq gpurun_out/$TAG/bench_pmc_fetch gpurun_out/$TAG/bench_pmc_write --source "profiles/${TAG}_bench_pmc_summary.txt (rocprofv3 --pmc, separate passes; python3 bench.py --no-cpu-baseline --no-extra --steps 3 --warmup 1 --no-prof)" > /dev/null
+python3 tools/pmc_stamp.py $OUT/bench_pmc_sq $OUT/bench_pmc_fetch $OUT/bench_pmc_write --source "profiles/${TAG}_bench_pmc_summary.txt (rocprofv3 --pmc, separate passes; python3 bench.py --full --no-cpu-baseline --no-extra --steps 3 --warmup 1 --no-prof)" > /dev/null
 cp profiles/pmc_head.json $OUT/pmc_head.json
 python3 tools/summarize_round.py gpurun_out/$TAG > $OUT/summary.txt 2>&1
 cat $OUT/summary.txt
@@ -59,7 +60,7 @@ if [ -f matrix-manifolds_amd/lib/variants/libmm_stamp.so ]; then
   MM_MANIFOLDS_LIB=/root/repo/matrix-manifolds_amd/lib/variants/libmm_stamp.so python3 tools/stamp_timeline.py 5000 --warm > $OUT/timeline_warm.txt 2>&1
   head -3 $OUT/timeline_cold.txt $OUT/timeline_warm.txt
 fi
-timeout 600 python3 bench.py > $OUT/bench.json 2> $OUT/bench.err
+timeout 600 python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 tail -c 400 $OUT/bench.json
 timeout 1200 python3 tools/bench_configs.py > $OUT/configs.json 2> $OUT/configs.err; echo "configs rc=$?"
 # node minibatches through the one-call step: the launches of a step (kernel trace of two of the cases)
@@ -74,4 +75,4 @@ fi
 python3 tools/shard_kernel_times.py > $OUT/shard_kernel_times.json 2> $OUT/shard.err
 python3 tools/eager_profile.py euclid > $OUT/eager_euclid.txt 2>&1
 python3 tools/eager_profile.py spd > $OUT/eager_spd.txt 2>&1
-MM_BENCH_BACKEND=gloo timeout 600 python3 bench.py --gpus 2 --steps 10 --warmup 3 --no-cpu-baseline > $OUT/bench_gloo2_dryrun.json 2> $OUT/bench_gloo2.err; echo "gloo2 rc=$?"
+MM_BENCH_BACKEND=gloo timeout 600 python3 bench.py --gpus 2 --steps 10 --warmup 3 --full --no-cpu-baseline > $OUT/bench_gloo2_dryrun.json 2> $OUT/bench_gloo2.err; echo "gloo2 rc=$?"
