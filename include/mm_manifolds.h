@@ -244,11 +244,14 @@ int mm_vec_pdist_fwd(int dtype, int kind, const void* x, int64_t n, int m, int64
 /* Same, forward only, with the Gram matrix X J X^T formed on the matrix cores
  * (v_mfma_f32_32x32x2_f32 / v_mfma_f64_16x16x4_f64) and the distance map fused
  * into the accumulator epilogue.  Lorentz and sphere (the reference evaluates
- * both from inner products); Euclidean uses the difference form above. */
+ * both from inner products); Euclidean uses the difference form above.  MM_ERR_UNSUPPORTED for n > 32768. */
 int mm_vec_pdist_fwd_gram(int dtype, int kind, const void* x, int64_t n, int m, int64_t row_begin,
                           int64_t row_end, int squared, void* out, mm_stream_t stream);
 /* Backward: grad_x [n,m] OVERWRITTEN with this shard's partial gradient.
- * (Sphere: the reference's 1/sqrt(1-c^2) is floored at 1e-8 instead of inf.) */
+ * (Sphere: the reference's 1/sqrt(1-c^2) is floored at 1e-8 instead of inf.)
+ * n > 2^22 returns MM_ERR_UNSUPPORTED (the balanced symmetric form stops there, and the ordered fallback launches one row of
+ * workgroups per 64 nodes of the whole problem whatever the row range); so does the ordered form (MM_VEC_BWD_ORDERED=1)
+ * beyond the device's grid height. */
 int mm_vec_pdist_bwd(int dtype, int kind, const void* x, const void* g, int64_t n, int m,
                      int64_t row_begin, int64_t row_end, int squared, void* grad_x, void* ws,
                      mm_stream_t stream);
@@ -262,7 +265,9 @@ int mm_vec_pdist_bwd_gram(int dtype, int kind, const void* x, const void* g, int
                           mm_stream_t stream);
 
 /* Fused objective + gradients for a single-factor vector-manifold embedding — the counterpart of
- * mm_spd_pdist_loss (same loss kinds, arguments and outputs; squared distances). */
+ * mm_spd_pdist_loss (same loss kinds, arguments and outputs; squared distances).  Where the symmetric pair kernel does
+ * not cover (dtype, kind, m) — fp32 m > 32, fp64 m > 16 except Euclidean (m > 32) — the ordered fallback serves it, and
+ * then n > 2^22 returns MM_ERR_UNSUPPORTED, as for mm_vec_pdist_bwd. */
 int mm_vec_pdist_loss(int dtype, int kind, int loss_kind, const void* x, const void* target,
                       const void* scale_raw, int64_t n, int m, int64_t row_begin, int64_t row_end,
                       double alpha, double eps, int terms, const double* loss_params, void* loss_out, void* grad_x, void* ws,

@@ -611,6 +611,14 @@ int vec_bwd_t(const T* x, const T* g, int64_t n, int m, int64_t rb, int64_t re, 
     else if (rc != MM_ERR_UNSUPPORTED) return rc;
   }
   if (!done) {
+    // The ordered kernel launches one row of workgroups per TI rows of the WHOLE problem, whatever the shard, and walks all n^2
+    // ordered pairs: beyond kSpdMaxNodes (where the symmetric form stops) or the device's grid height it is refused, not launched.
+    {
+      int dev = 0, max_y = 0;
+      if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&max_y, hipDeviceAttributeMaxGridDimY, dev) != hipSuccess || max_y < 1)
+        max_y = 65535;
+      if (n > kSpdMaxNodes || (n + TI - 1) / TI > int64_t(max_y)) return MM_ERR_UNSUPPORTED;
+    }
     hipError_t e = hipMemsetAsync(acc, 0, sizeof(T) * (size_t(n) * (MP + 1) + 2 * kLossSlots), st);
     if (e != hipSuccess) return int(e);
     la.slots = slots;

@@ -765,6 +765,7 @@ extern "C" int mm_vec_pdist_fwd_gram(int dtype, int kind, const void* x, int64_t
                                      int64_t row_end, int squared, void* out, mm_stream_t stream) {
   if (!x || n < 0 || m < 1 || row_begin < 0 || row_end > n || row_begin > row_end || n > (1 << 30)) return MM_ERR_ARG;
   if (kind != MM_LORENTZ && kind != MM_SPHERE) return MM_ERR_UNSUPPORTED;
+  if (n > 32768) return MM_ERR_UNSUPPORTED;   // (the range of vec_gram_supports, which the Python layer keeps to)
   if (!out && mm_pair_offset(n, row_end) > mm_pair_offset(n, row_begin)) return MM_ERR_ARG;
   if (row_end <= row_begin) return MM_OK;
   hipStream_t st = static_cast<hipStream_t>(stream);

@@ -13,7 +13,10 @@
  * Pinned by tests/test_oracle_exact.py against oracle/ref_port.py in fp64 (itself pinned against
  * the reference's golden vectors) — agreement to the reference's own eps bias.
  *
- * Eigen-decomposition: cyclic Jacobi to machine precision.  OpenMP over rows.
+ * The *_pairs / *_pairs_grad entry points evaluate the same formulas on an explicit pair list (the large-n tests check
+ * samples of launches whose whole pdist is out of reach); pinned against the whole-pdist ones by the same test file.
+ *
+ * Eigen-decomposition: cyclic Jacobi to machine precision.  OpenMP over rows (over pairs for the pair lists).
  * Build: make -C oracle   ->  oracle/_build/liboracle_exact.so
  */
 #include <math.h>
@@ -169,6 +172,83 @@ int oracle_spd_pdist_grad(const double* x, const double* g, long n, int d, int s
   return bad ? -3 : 0;
 }
 
+/* ---- explicit pair lists: pair k is (lo[k], hi[k]), lo[k] < hi[k] < n — what the large-n tests sample from launches whose
+ * whole pdist the functions above cannot afford.  Nothing is precomputed per node (n may be 2^22 while the list holds a few rows'
+ * pairs): each pair factors its own two points.  The gradient is evaluated in chunks of pairs, in parallel, into a per-chunk
+ * buffer that is then added into `grad` in pair order — memory independent of n, and the same result for any thread count. */
+static int spd_pair_eval(int d, const double* x, long i, long j, double wmin, double wmax, double li[DMAX][DMAX],
+                         double v[DMAX][DMAX], double w[DMAX], double lw[DMAX], double rho[DMAX], double* s) {
+  double xsi[DMAX][DMAX], xsj[DMAX][DMAX], lj[DMAX][DMAX];
+  if (!inv_chol(d, x + i * d * d, li, xsi) || !inv_chol(d, x + j * d * d, lj, xsj)) return 0;
+  *s = pair_eig(d, li, xsj, wmin, wmax, v, w, lw, rho);
+  return 1;
+}
+
+static int pairs_ok(long n, const long* lo, const long* hi, long count) {
+  for (long k = 0; k < count; ++k) if (lo[k] < 0 || lo[k] >= hi[k] || hi[k] >= n) return 0;
+  return 1;
+}
+
+int oracle_spd_pairs(const double* x, long n, int d, const long* lo, const long* hi, long count, int squared, double wmin,
+                     double wmax, double* out) {
+  if (d > DMAX) return -2;
+  if (!pairs_ok(n, lo, hi, count)) return -1;
+  int bad = 0;
+#pragma omp parallel for schedule(dynamic, 256) reduction(| : bad)
+  for (long k = 0; k < count; ++k) {
+    double li[DMAX][DMAX], v[DMAX][DMAX], w[DMAX], lw[DMAX], s;
+    if (!spd_pair_eval(d, x, lo[k], hi[k], wmin, wmax, li, v, w, lw, NULL, &s)) { bad = 1; continue; }
+    s = fmax(s, wmin);
+    out[k] = squared ? s : sqrt(s);
+  }
+  return bad ? -3 : 0;
+}
+
+int oracle_spd_pairs_grad(const double* x, long n, int d, const long* lo, const long* hi, const double* g, long count,
+                          int squared, double wmin, double wmax, double* grad) {
+  if (d > DMAX) return -2;
+  if (!pairs_ok(n, lo, hi, count)) return -1;
+  const long dd = (long)d * d, chunk = 1L << 18;
+  double* buf = malloc(sizeof(double) * 2 * dd * (count < chunk ? (count > 0 ? count : 1) : chunk));
+  if (!buf) return -4;
+  memset(grad, 0, sizeof(double) * n * dd);
+  int bad = 0;
+  for (long k0 = 0; k0 < count; k0 += chunk) {
+    const long k1 = count < k0 + chunk ? count : k0 + chunk;
+#pragma omp parallel for schedule(dynamic, 256) reduction(| : bad)
+    for (long k = k0; k < k1; ++k) {
+      double li[DMAX][DMAX], v[DMAX][DMAX], w[DMAX], lw[DMAX], rho[DMAX], m[DMAX][DMAX], nn[DMAX][DMAX], t[DMAX][DMAX], s;
+      double* dst0 = buf + (k - k0) * 2 * dd;
+      if (!spd_pair_eval(d, x, lo[k], hi[k], wmin, wmax, li, v, w, lw, rho, &s)) { bad = 1; memset(dst0, 0, sizeof(double) * 2 * dd); continue; }
+      double gs = g[k];
+      if (!squared) gs *= 0.5 / sqrt(fmax(s, wmin));
+      for (int r = 0; r < d; ++r) for (int c = 0; c < d; ++c) {
+        double a = 0, b = 0;
+        for (int q = 0; q < d; ++q) { a += v[r][q] * (2 * gs * lw[q] * rho[q]) * v[c][q]; b += v[r][q] * (2 * gs * lw[q] / w[q]) * v[c][q]; }
+        m[r][c] = a; nn[r][c] = b;
+      }
+      /* d/dX_lo = -Li^T M Li ; d/dX_hi = Li^T N Li  (as oracle_spd_pdist_grad) */
+      for (int pass = 0; pass < 2; ++pass) {
+        double (*src)[DMAX] = pass ? nn : m;
+        for (int r = 0; r < d; ++r) for (int c = 0; c < d; ++c) { double a = 0; for (int q = r; q < d; ++q) a += li[q][r] * src[q][c]; t[r][c] = a; }
+        double* dst = dst0 + pass * dd;
+        for (int r = 0; r < d; ++r) for (int c = 0; c < d; ++c) {
+          double a = 0; for (int q = c; q < d; ++q) a += t[r][q] * li[q][c];
+          dst[r * d + c] = pass ? a : -a;
+        }
+      }
+    }
+    for (long k = k0; k < k1; ++k) {
+      const double* src = buf + (k - k0) * 2 * dd;
+      double* gi = grad + lo[k] * dd;
+      double* gj = grad + hi[k] * dd;
+      for (long e = 0; e < dd; ++e) { gi[e] += src[e]; gj[e] += src[dd + e]; }
+    }
+  }
+  free(buf);
+  return bad ? -3 : 0;
+}
+
 /* kind: 0 Euclidean, 1 Lorentz, 2 Sphere */
 static double vec_q(int kind, const double* a, const double* b, int m) {
   double q = 0;
@@ -220,6 +300,54 @@ int oracle_vec_pdist_grad(int kind, const double* x, const double* g, long n, in
     for (size_t k = 0; k < (size_t)n * m; ++k) grad[k] += loc[k];
     free(loc);
   }
+  return 0;
+}
+
+/* vector manifolds on explicit pair lists (as the SPD ones above) */
+static void vec_pair_grad(int kind, const double* xi_, const double* xj_, int m, double w, double* gi, double* gj) {
+  for (int k = 0; k < m; ++k) {
+    const double xi = xi_[k], xj = xj_[k];
+    double ai, aj;
+    if (kind == 0) { ai = 2 * (xi - xj); aj = -ai; }
+    else if (kind == 1) { ai = k ? -xj : xj; aj = k ? -xi : xi; }
+    else { ai = xj; aj = xi; }
+    gi[k] = w * ai; gj[k] = w * aj;
+  }
+}
+
+int oracle_vec_pairs(int kind, const double* x, long n, int m, const long* lo, const long* hi, long count, int squared,
+                     double* out) {
+  if (!pairs_ok(n, lo, hi, count)) return -1;
+#pragma omp parallel for schedule(static, 4096)
+  for (long k = 0; k < count; ++k) { double dq; out[k] = vec_val(kind, vec_q(kind, x + lo[k] * m, x + hi[k] * m, m), squared, &dq); }
+  return 0;
+}
+
+int oracle_vec_pairs_grad(int kind, const double* x, long n, int m, const long* lo, const long* hi, const double* g, long count,
+                          int squared, double* grad) {
+  if (!pairs_ok(n, lo, hi, count)) return -1;
+  const long chunk = 1L << 18;
+  double* buf = malloc(sizeof(double) * 2 * m * (count < chunk ? (count > 0 ? count : 1) : chunk));
+  if (!buf) return -4;
+  memset(grad, 0, sizeof(double) * n * m);
+  for (long k0 = 0; k0 < count; k0 += chunk) {
+    const long k1 = count < k0 + chunk ? count : k0 + chunk;
+#pragma omp parallel for schedule(static, 1024)
+    for (long k = k0; k < k1; ++k) {
+      const double* xi = x + lo[k] * m, *xj = x + hi[k] * m;
+      double dq;
+      vec_val(kind, vec_q(kind, xi, xj, m), squared, &dq);
+      double* dst = buf + (k - k0) * 2 * m;
+      vec_pair_grad(kind, xi, xj, m, g[k] * dq, dst, dst + m);
+    }
+    for (long k = k0; k < k1; ++k) {
+      const double* src = buf + (k - k0) * 2 * m;
+      double* gi = grad + lo[k] * m;
+      double* gj = grad + hi[k] * m;
+      for (int e = 0; e < m; ++e) { gi[e] += src[e]; gj[e] += src[m + e]; }
+    }
+  }
+  free(buf);
   return 0;
 }
 

@@ -53,3 +53,84 @@ def test_spd4_against_port_seeded():
     assert np.abs(exact.spd_pdist_grad(x.numpy(), g.numpy()) - ref).max() <= 1e-9 * np.abs(ref).max()
     with pytest.raises(np.linalg.LinAlgError):
         exact.spd_pdist(-np.eye(3)[None].repeat(3, 0))
+
+
+def _pair_subsets(n, gen):
+    """Every pair, a random subset (with repeats, in random order) and the empty list."""
+    iu = np.triu_indices(n, 1)
+    k = gen.integers(0, iu[0].size, size=3 * n)
+    return [(iu[0], iu[1]), (iu[0][k], iu[1][k]), (iu[0][:0], iu[1][:0])]
+
+
+def _grad_over_subset(full_grad_fn, n, lo, hi, gk):
+    """The whole-pdist gradient with g zero outside the list (repeated pairs add up): what the pair-list gradient must equal."""
+    g = np.zeros(n * (n - 1) // 2)
+    np.add.at(g, exact.pair_index(n, lo, hi), gk)
+    return full_grad_fn(g)
+
+
+@pytest.mark.parametrize('d', [2, 3, 4, 6, 9])
+@pytest.mark.parametrize('squared', [True, False])
+def test_spd_pair_lists_match_pdist(d, squared):
+    gen = np.random.default_rng(10 * d + squared)
+    n = 41
+    x = rp.SPD(d).rand(n, dtype=torch.float64, generator=torch.Generator().manual_seed(d)).numpy()
+    full = exact.spd_pdist(x, squared=squared)
+    for lo, hi in _pair_subsets(n, gen):
+        k = exact.pair_index(n, lo, hi)
+        out = exact.spd_pairs(x, lo, hi, squared=squared)
+        np.testing.assert_allclose(out, full[k], rtol=1e-13, atol=1e-15)
+        gk = gen.standard_normal(lo.size)
+        ref = _grad_over_subset(lambda g: exact.spd_pdist_grad(x, g, squared=squared), n, lo, hi, gk)
+        got = exact.spd_pairs_grad(x, lo, hi, gk, squared=squared)
+        scale = max(np.abs(ref).max(), 1e-300)
+        assert np.abs(got - ref).max() <= 1e-12 * scale
+        untouched = np.setdiff1d(np.arange(n), np.concatenate([lo, hi]))
+        assert (got[untouched] == 0).all()
+
+
+@pytest.mark.parametrize('kind,m', [('lorentz', 11), ('sphere', 2), ('sphere', 64), ('euclidean', 11)])
+@pytest.mark.parametrize('squared', [True, False])
+def test_vec_pair_lists_match_pdist(kind, m, squared):
+    gen = np.random.default_rng(m + squared)
+    n = 53
+    x = gen.standard_normal((n, m))
+    if kind == 'sphere':
+        x /= np.linalg.norm(x, axis=1, keepdims=True)
+    elif kind == 'lorentz':
+        x[:, 0] = np.sqrt(1 + (x[:, 1:] ** 2).sum(1))
+    full = exact.vec_pdist(kind, x, squared)
+    for lo, hi in _pair_subsets(n, gen):
+        k = exact.pair_index(n, lo, hi)
+        np.testing.assert_allclose(exact.vec_pairs(kind, x, lo, hi, squared), full[k], rtol=1e-14, atol=0)
+        gk = gen.standard_normal(lo.size)
+        ref = _grad_over_subset(lambda g: exact.vec_pdist_grad(kind, x, g, squared), n, lo, hi, gk)
+        got = exact.vec_pairs_grad(kind, x, lo, hi, gk, squared)
+        assert np.abs(got - ref).max() <= 1e-12 * max(np.abs(ref).max(), 1e-300)
+
+
+def test_pair_index_round_trip_at_large_n():
+    """pair_index / pair_of_index (the large-n tests' sampling arithmetic) are exact inverses, at the row boundaries and
+    around 2^31 and 2^32 / 4 of the largest sizes the GPU tests address."""
+    for n in (2, 3, 65600, 70000, 1 << 22, 1 << 24):
+        total = n * (n - 1) // 2
+        ks = {0, total - 1, total // 2}
+        for c in (2 ** 31, 2 ** 30, 2 ** 29):
+            ks.update(v for v in (c - 1, c, c + 1) if 0 <= v < total)
+        rows = np.array([0, 1, n // 2, n - 2])
+        rows = rows[(rows >= 0) & (rows <= n - 2)]
+        for r in rows:
+            ks.update({int(exact.pair_index(n, r, r + 1)), int(exact.pair_index(n, r, n - 1))})
+        k = np.array(sorted(ks), dtype=np.int64)
+        lo, hi = exact.pair_of_index(n, k)
+        assert ((lo >= 0) & (lo < hi) & (hi < n)).all(), n
+        assert (exact.pair_index(n, lo, hi) == k).all(), n
+
+
+def test_pair_lists_refuse_bad_pairs():
+    x = np.eye(3)[None].repeat(4, 0)
+    for lo, hi in (([1], [1]), ([2], [1]), ([0], [4]), ([-1], [2])):
+        with pytest.raises(ValueError):
+            exact.spd_pairs(x, lo, hi)
+    with pytest.raises(np.linalg.LinAlgError):
+        exact.spd_pairs(-np.eye(3)[None].repeat(3, 0), [0], [1])
