@@ -16,4 +16,8 @@ Two restatements live here:
   evaluation of the same mathematical formulas (cyclic Jacobi eigensolver,
   analytic gradients).  Pinned against ``ref_port`` fp64 and the same golden
   vectors; used for full-size checks because it runs in seconds.
+
+``oracle.step`` builds ONE whole training step in fp64 on top of both (exact.c
+distances, numpy losses, the port's optimizer maps with LAPACK factorisations):
+the checker of the step kernels, pinned by ``tests/test_oracle_step.py``.
 """

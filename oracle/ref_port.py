@@ -548,6 +548,35 @@ def rsgd_step(man, x, grad, *, lr, momentum=0.0, dampening=0.0,
         return step(x, -lr * g), None  # rsgd.py:82
 
 
+def radam_step(man, x, grad, state, *, lr, betas=(0.9, 0.999), nc=False, max_grad_norm=None, exact=False):
+    """One RiemannianAdam update of one parameter — optim/radam.py:43-98.
+
+    ``state`` is the optimizer's per-parameter dict (``step``, ``exp_avg``, ``exp_avg_sq``; created when
+    empty, radam.py:55-60) and is updated in place; ``exp_avg_sq`` holds one scalar per point, broadcast
+    over it.  Returns ``new_x``.
+    """
+    with torch.no_grad():
+        if not state:
+            state.update(step=1, exp_avg=torch.zeros_like(x), exp_avg_sq=torch.zeros_like(x))
+        beta1, beta2 = betas
+        g = man.egrad2rgrad(x, grad)
+        gn = man.norm(x, g, keepdim=True)  # the second moment sees the norm BEFORE clipping (radam.py:72-74)
+        if max_grad_norm is not None:
+            g = g * torch.clamp(max_grad_norm / gn, max=1.0)
+        t = state['step']
+        if nc:  # radam.py:82-83
+            beta2 = 1 - 1 / t
+        m = state['exp_avg'] * beta1 + (1 - beta1) * g
+        v = state['exp_avg_sq'] * beta2 + (1 - beta2) * gn.pow(2)
+        alpha = lr * (1 - beta2**t)**0.5 / (1 - beta1**t)
+        direction = -alpha * m / (v.sqrt() + EPS)
+        new_x = (man.exp if exact else man.retr)(x, direction)
+        state['exp_avg'] = man.transp(x, new_x, m)
+        state['exp_avg_sq'] = v
+        state['step'] = t + 1
+        return new_x
+
+
 def compute_dists(mans, xs, scales, idx=None):
     """ManifoldEmbedding.compute_dists — modules.py:84-88."""
     sp = torch.nn.functional.softplus

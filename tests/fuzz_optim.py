@@ -16,31 +16,6 @@ from graphembed.modules import ManifoldParameter  # noqa: E402
 from graphembed.optim import RiemannianAdam, RiemannianSGD  # noqa: E402
 from oracle import ref_port as rp  # noqa: E402
 
-EPS = 1e-8
-
-
-def ref_adam(man, x, g, state, *, lr, betas, nc, clip, exact):
-    """optim/radam.py:62-98 on the port's manifolds."""
-    if not state:
-        state.update(step=1, m=torch.zeros_like(x), v=torch.zeros_like(x))
-    beta1, beta2 = betas
-    rg = man.egrad2rgrad(x, g)
-    nrm = man.norm(x, rg, keepdim=True)
-    if clip is not None:
-        rg = rg * torch.clamp(clip / nrm, max=1.0)
-    t = state['step']
-    if nc:
-        beta2 = 1 - 1 / t
-    state['m'] = state['m'] * beta1 + (1 - beta1) * rg
-    state['v'] = state['v'] * beta2 + (1 - beta2) * nrm.pow(2)
-    alpha = lr * (1 - beta2**t)**0.5 / (1 - beta1**t)
-    direction = -alpha * state['m'] / (state['v'].sqrt() + EPS)
-    new_x = (man.exp if exact else man.retr)(x, direction)
-    state['m'] = man.transp(x, new_x, state['m'])
-    state['step'] = t + 1
-    return new_x
-
-
 def main():
     cases = int(sys.argv[1]) if len(sys.argv) > 1 else 200
     rng = random.Random(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
@@ -98,7 +73,7 @@ def main():
                     xr = rx[i].reshape(-1, rx[i].shape[-1] if rx[i].ndim else 1) if flat else rx[i]
                     gr = g.reshape(xr.shape)
                     if adam:
-                        new = ref_adam(ref, xr, gr, rstate[i], lr=lr, betas=betas, nc=nc, clip=clip, exact=exact)
+                        new = rp.radam_step(ref, xr, gr, rstate[i], lr=lr, betas=betas, nc=nc, max_grad_norm=clip, exact=exact)
                     else:
                         new, rbuf[i] = rp.rsgd_step(ref, xr, gr, lr=lr, momentum=momentum, dampening=damp,
                                                     max_grad_norm=clip, exact=exact, momentum_buffer=rbuf[i])
