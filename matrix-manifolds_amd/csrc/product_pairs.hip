@@ -86,15 +86,11 @@ __global__ __launch_bounds__(kPCols * kPWaves) void product_pair_kernel(PArgs<T>
   // XCD-aware tile order: the eight XCDs have private L2s and workgroups are dealt to them round-robin, so the workgroups
   // that share an XCD (orig % 8: a group label, not the XCD's id) take a CONTIGUOUS run of tiles in row-major order — a band
   // of row tiles — and the band's targets (its rows of the pair vector, and its columns of the rows above) are fetched into
-  // one L2 instead of all eight (bijective for any grid size).  -DMM_PRODUCT_NO_XCD: the plain order (A/B builds).
-#ifdef MM_PRODUCT_NO_XCD
-  const unsigned bx = blockIdx.x, by = blockIdx.y;
-#else
+  // one L2 instead of all eight (bijective for any grid size).
   const unsigned nwg = gridDim.x * gridDim.y, orig = blockIdx.y * gridDim.x + blockIdx.x;
   const unsigned xq = nwg / 8, xr = nwg % 8, xcd = orig % 8;
   const unsigned tile = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + orig / 8;
   const unsigned bx = tile % gridDim.x, by = tile / gridDim.x;
-#endif
   const int j = bx * kPCols + lane;
   const int i0 = min(int((by * kPWaves + wave) * ti), n), i1 = min(i0 + ti, n);
   const bool jin = j < n;

@@ -114,11 +114,8 @@ template <uint64_t BITS> __device__ __forceinline__ double fma_sconst64(double a
 // one scalar load, spilled and reloaded in front of every use.
 template <typename T, typename TAB, int I> __device__ __forceinline__ T fma_coef(T a, T b) {
   constexpr T c = TAB::at(I);
-#ifndef MM_F64_CONST_VGPR   // (A/B builds: the compiler's placement)
   if constexpr (std::is_same<T, double>::value) return fma_sconst64<__builtin_bit_cast(uint64_t, c)>(a, b);
-  else
-#endif
-    return Num<T>::fma(a, b, c);
+  else return Num<T>::fma(a, b, c);
 }
 // Horner's rule in the quotient ring R[E]/(chi_E) of a 3x3 matrix, chi_E = x^3 - s1 x^2 + s2 x - s3: on exit
 // a0 I + a1 E + a2 E^2 = TAB[0] I + TAB[1] E + ... + TAB[N-1] E^(N-1).  One step, (a0, a1, a2) . E + c I =
@@ -405,11 +402,7 @@ __device__ __forceinline__ void jacobi_eig(T (&a)[Packed<D>::NP], T (&v)[D][D], 
   // (D >= 6: the sweeps stay a loop — unrolled, a 9x9 solve with eigenvectors is ~30 000 instructions per call site —
   // and get a few more of them: the quadratic convergence of cyclic Jacobi starts later for larger matrices)
   constexpr int kSweeps = D <= 5 ? N::kMaxSweeps : N::kMaxSweeps + 4;
-#ifdef MM_JACOBI_ROLL_F64   // (A/B builds: the fp64 sweeps as a loop — the unrolled fp64 backward is 73 KB of code)
-  constexpr int kUnrollSweeps = (D <= 5 && !std::is_same<T, double>::value) ? N::kMaxSweeps : 1;
-#else
   constexpr int kUnrollSweeps = D <= 5 ? N::kMaxSweeps : 1;
-#endif
 #pragma unroll kUnrollSweeps
   for (int sweep = 0; sweep < kSweeps; ++sweep) {
     bool active = sweep < kMinSweeps;
@@ -781,16 +774,6 @@ template <typename T> __device__ __forceinline__ T ldexp_t(T x, int k);
 template <> __device__ __forceinline__ float ldexp_t<float>(float x, int k) { return ::ldexpf(x, k); }
 template <> __device__ __forceinline__ double ldexp_t<double>(double x, int k) { return ::ldexp(x, k); }
 
-template <typename T> __device__ __forceinline__ void sym3_mul(const T (&x)[6], const T (&y)[6], T (&o)[6]) {
-  using N = Num<T>;  // product of two COMMUTING symmetric 3x3 (packed 00,10,11,20,21,22)
-  o[0] = N::fma(x[0], y[0], N::fma(x[1], y[1], x[3] * y[3]));
-  o[1] = N::fma(x[1], y[0], N::fma(x[2], y[1], x[4] * y[3]));
-  o[2] = N::fma(x[1], y[1], N::fma(x[2], y[2], x[4] * y[4]));
-  o[3] = N::fma(x[3], y[0], N::fma(x[4], y[1], x[5] * y[3]));
-  o[4] = N::fma(x[3], y[1], N::fma(x[4], y[2], x[5] * y[4]));
-  o[5] = N::fma(x[3], y[3], N::fma(x[4], y[4], x[5] * y[5]));
-}
-
 // ---- the same logarithm with the matrix algebra moved into quotient rings (round 4) ------------------------------
 // Everything between E^2 and the last combination is scalar arithmetic (tools/design/cayley_ring.py):
 //   mu = 2^k,  E = A / mu - I (exact scaling),  s1, s2, s3 = elementary symmetric functions of E's spectrum,
@@ -802,7 +785,7 @@ template <typename T> __device__ __forceinline__ void sym3_mul(const T (&x)[6], 
 //            = g0 + g1 E + g2 E^2      (Z, Z^2 written in the E basis by ring arithmetic on their coefficients),
 //   log A = log(mu) I + 2 (g0 I + g1 E + g2 E^2).
 // Matrix work: E^2 (18 FMAs) and the last line (12) — against the adjugate, three commuting 3x3 products and the assembly
-// of P(W) (~105) in log_cayley3_matrix; ~146 operations in all against ~180, six matrix temporaries fewer alive, and the
+// of P(W) (~105) of the round-1..3 form; ~146 operations in all against ~180, six matrix temporaries fewer alive, and the
 // gate tr(Z^2) is known before any matrix is formed.  Accuracy (emulated, against a 40-digit eigendecomposition): 5e-7
 // of max|log A| in fp32, 7e-15 in fp64, spectra of any spread inside the gate and mu up to 2^+-11.
 // `pre` multiplies log A (the caller's 2g when it is known before the logarithm).
@@ -886,13 +869,12 @@ template <typename T> __device__ __forceinline__ T log_cayley3(const T (&a)[6], 
   cayley3_spectrum<T>(s1, s2, s3, rD, z1, z2, z3, t1, t2, t3);
   // P(W) = c0 + c1 W + c2 W^2 by Horner in R[W]/(chi_W), W^3 = t1 W^2 - t2 W + t3 I
   T c0, c1, c2;
-#ifndef MM_CAYLEY_ONE_TIER   // (A/B builds)
   if constexpr (std::is_same<T, double>::value) {
     if (!__any(!(t1 <= T(kCayleyNarrow)))) ring_horner3<T, CayleyPn64>(t1, t2, t3, c0, c1, c2);
     else ring_horner3<T, P>(t1, t2, t3, c0, c1, c2);
-  } else
-#endif
+  } else {
     ring_horner3<T, P>(t1, t2, t3, c0, c1, c2);
+  }
   // Z (c2 Z^4 + c1 Z^2 + c0) in R[Z]/(chi_Z), Z^3 = z1 Z^2 - z2 Z + z3 I: start from c2 Z^2 + c1, then . Z, . Z + c0, . Z
   T b0 = c2 * z3, b1 = N::fma(-c2, z2, c1), b2 = c2 * z1;
   {
@@ -966,77 +948,14 @@ template <typename T> __device__ __forceinline__ T logsq_cayley3(const T (&a)[6]
   *gate = t1;
   const T p1 = t1, p2 = N::fma(t1, p1, T(-2) * t2), p3 = N::fma(t1, p2, N::fma(-t2, p1, T(3) * t3));
   T c0, c1, c2;
-#ifndef MM_CAYLEY_ONE_TIER
   if constexpr (std::is_same<T, double>::value) {
     if (!__any(!(t1 <= T(kCayleyNarrow)))) ring_horner3<T, CayleyQn64>(t1, t2, t3, c0, c1, c2);
     else ring_horner3<T, Q>(t1, t2, t3, c0, c1, c2);
-  } else
-#endif
+  } else {
     ring_horner3<T, Q>(t1, t2, t3, c0, c1, c2);
+  }
   const T s = N::fma(c2, p3, N::fma(c1, p2, c0 * p1));   // sum atanh^2 z_k
   return N::fma(logmu, N::fma(T(-3), logmu, logdet_a + logdet_a), T(4) * s);
-}
-
-// (the round-1..3 form, kept for A/B builds: -DMM_CAYLEY_MATRIX)
-template <typename T> __device__ __forceinline__ T log_cayley3_matrix(const T (&a)[6], T (&m0)[6]) {
-  using N = Num<T>;
-  constexpr bool kF32 = std::is_same<T, float>::value;
-  constexpr int K = kF32 ? 6 : 13;
-  constexpr double kC32[7] = {1.00000002318570891e+00, 3.33327042495924375e-01, 2.00274867564608688e-01,
-                              1.38428695737667723e-01, 1.44240977093542333e-01, -3.05379184438951401e-02,
-                              2.73482843603638170e-01};
-  constexpr double kC64[14] = {9.99999999999997002e-01, 3.33333333336093829e-01, 1.99999999512113669e-01,
-                               1.42857176992888746e-01, 1.11109865194520263e-01, 9.09362522505209464e-02,
-                               7.65413194323763535e-02, 7.02835946952955759e-02, 3.51739351378960174e-02,
-                               1.60038305495638411e-01, -2.87332526616183470e-01, 7.35063731671786291e-01,
-                               -8.29196169410508666e-01, 5.70221868872885063e-01};
-  int k;
-  const T mant = frexp_t<T>((a[0] + a[2] + a[5]) * T(1.0 / 3.0), &k);  // mean eigenvalue = mant 2^k
-  if (mant < T(0.70710678118654752)) k -= 1;
-  const T mu = ldexp_t<T>(T(1), k), logmu = T(k) * T(0.69314718055994531);
-  // adj(B), B = A + mu I
-  const T b00 = a[0] + mu, b11 = a[2] + mu, b22 = a[5] + mu, b10 = a[1], b20 = a[3], b21 = a[4];
-  T adj[6], e[6], z[6], w[6], w2[6];
-  adj[0] = N::fma(b11, b22, -b21 * b21);
-  adj[1] = N::fma(b21, b20, -b10 * b22);
-  adj[2] = N::fma(b00, b22, -b20 * b20);
-  adj[3] = N::fma(b10, b21, -b11 * b20);
-  adj[4] = N::fma(b10, b20, -b00 * b21);
-  adj[5] = N::fma(b00, b11, -b10 * b10);
-  const T rdet = N::rcp(N::fma(b00, adj[0], N::fma(b10, adj[1], b20 * adj[3])));
-  e[0] = a[0] - mu; e[1] = a[1]; e[2] = a[2] - mu; e[3] = a[3]; e[4] = a[4]; e[5] = a[5] - mu;
-  sym3_mul<T>(e, adj, z);
-#pragma unroll
-  for (int i = 0; i < 6; ++i) z[i] *= rdet;
-  sym3_mul<T>(z, z, w);
-  sym3_mul<T>(w, w, w2);
-  const T t1 = w[0] + w[2] + w[5];
-  const T t2 = T(0.5) * N::fma(t1, t1, -(w2[0] + w2[2] + w2[5]));
-  const T t3 = w[0] * N::fma(w[2], w[5], -w[4] * w[4]) - w[1] * N::fma(w[1], w[5], -w[4] * w[3]) +
-               w[3] * N::fma(w[1], w[4], -w[2] * w[3]);
-  auto cf = [&](int i) -> T { return kF32 ? T(kC32[i < 7 ? i : 0]) : T(kC64[i]); };
-  // P(W) = sum coef_i W^i by Horner's rule in R[W]/(chi_W) (see log_series3): three FMAs per coefficient
-  T c0 = cf(K - 2), c1 = cf(K - 1), c2 = cf(K);
-#pragma unroll
-  for (int i = K - 3; i >= 0; --i) {
-    const T n0 = N::fma(c2, t3, cf(i)), n1 = N::fma(-c2, t2, c0), n2 = N::fma(c2, t1, c1);
-    c0 = n0; c1 = n1; c2 = n2;
-  }
-  T pw[6];
-  pw[0] = N::fma(c2, w2[0], N::fma(c1, w[0], c0));
-  pw[1] = N::fma(c2, w2[1], c1 * w[1]);
-  pw[2] = N::fma(c2, w2[2], N::fma(c1, w[2], c0));
-  pw[3] = N::fma(c2, w2[3], c1 * w[3]);
-  pw[4] = N::fma(c2, w2[4], c1 * w[4]);
-  pw[5] = N::fma(c2, w2[5], N::fma(c1, w[5], c0));
-  sym3_mul<T>(z, pw, m0);
-  m0[0] = N::fma(T(2), m0[0], logmu);
-  m0[1] += m0[1];
-  m0[2] = N::fma(T(2), m0[2], logmu);
-  m0[3] += m0[3];
-  m0[4] += m0[4];
-  m0[5] = N::fma(T(2), m0[5], logmu);
-  return t1;
 }
 
 // product of two COMMUTING symmetric DxD matrices (packed lower), D x (D+1)/2 x D FMAs
@@ -1110,13 +1029,9 @@ __device__ __forceinline__ void log_series_mat(const T (&e)[Packed<D>::NP], T (&
 // groups of four unless they save nothing (K = 8: five products either way) or the six matrices do not fit beside the kernel's
 // own state and spill inside the group loop (measured per size and precision: profiles/r05_experiments.md §18)
 template <typename T, int D, typename S> constexpr int series_group() {
-#ifdef MM_SERIES_GROUP   // (A/B builds)
-  return MM_SERIES_GROUP;
-#else
   if (S::kTerms <= 8) return 2;
   if (sizeof(T) == 4) return D <= 7 ? 4 : 2;
   return (D == 5 || (D == 6 && S::kTerms <= 20)) ? 4 : 2;
-#endif
 }
 // close pairs (||A - I||_F <= 0.3, the caller's gate)
 template <typename T, int D> __device__ __forceinline__ void log_close_mat(const T (&a)[Packed<D>::NP], T (&m0)[Packed<D>::NP]) {

@@ -135,7 +135,6 @@ __device__ __forceinline__ T pair_core(const TL (&li)[Packed<D>::NP], const T (&
 #pragma unroll
     for (int k = 0; k < D; ++k) ev[k] = a[pidx(k, k)];
   }
-#ifndef MM_SPD_JACOBI_TWO_SIDED   // (A/B builds: the round-1..3 route only)
   if constexpr (SECOND && CHOL && D <= 4 && std::is_same<T, float>::value) {
     // fp32, ill-conditioned pairs: forming A = B B^T (B = L_i^-1 L_j) costs eps cond(A) of relative accuracy in A's small
     // eigenvalues whatever solves it afterwards — 1.2 (!) of d^2 at cond(X) = 1e4, where fp64 is fine.  A wavefront that
@@ -183,7 +182,6 @@ __device__ __forceinline__ T pair_core(const TL (&li)[Packed<D>::NP], const T (&
       }
     }
   }
-#endif
   T s = T(0);
 #pragma unroll
   for (int k = 0; k < D; ++k) {
@@ -242,16 +240,10 @@ template <typename T, int D> __device__ __forceinline__ void log_close(const T (
 }
 // `pre` multiplies log A (folded into three scalars by the 3x3 ring form; 4x4: applied to the matrix)
 template <typename T, int D> __device__ __forceinline__ T log_cayley(const T (&a)[Packed<D>::NP], T (&m0)[Packed<D>::NP], T pre = T(1)) {
-#ifdef MM_CAYLEY_MATRIX   // (A/B builds: the round-3 form with the adjugate and three matrix products)
-  constexpr bool kRing = false;
-#else
-  constexpr bool kRing = D == 3;
-#endif
-  if constexpr (kRing) {
+  if constexpr (D == 3) {
     return log_cayley3<T>(a, m0, pre);
   } else {
-    T gate;
-    if constexpr (D == 3) gate = log_cayley3_matrix<T>(a, m0); else gate = log_cayley4<T>(a, m0);
+    const T gate = log_cayley4<T>(a, m0);
 #pragma unroll
     for (int k = 0; k < Packed<D>::NP; ++k) m0[k] *= pre;
     return gate;
@@ -259,11 +251,7 @@ template <typename T, int D> __device__ __forceinline__ T log_cayley(const T (&a
 }
 // the forward's far path takes the invariants-only form where log det A is at hand (all-pairs kernels: per-node table)
 template <typename T, int D> constexpr bool fwd_uses_logdet() {
-#ifdef MM_CAYLEY_MATRIX
-  return false;
-#else
   return D == 3 && std::is_same<T, double>::value;
-#endif
 }
 
 // The reference clamps the eigenvalues of A to [wmin, wmax] (value only, spd.py:29-30, 163-169; defaults 1e-8 / 1e8).  The
@@ -277,11 +265,6 @@ __host__ __device__ inline bool spd_clamps_wide(double wmin, double wmax) { retu
 template <int D, int LOSS> inline bool spd_clamps_supported(double wmin, double wmax) {
   return (D <= 2 && LOSS == MM_LOSS_NONE) || spd_clamps_wide(wmin, wmax);
 }
-#ifdef MM_SPD_NO_SERIES_MAT   // (A/B builds: SPD(5 .. 9) on the Jacobi route of rounds 1-4)
-constexpr bool kSeriesMat = false;
-#else
-constexpr bool kSeriesMat = true;
-#endif
 // Forward-only value of one pair.  SPD(3) in fp32 takes the closed-form (trigonometric)
 // eigenvalues; a wavefront in which any pair has a wide spectrum (w_max > 32 w_min, where
 // the closed form's absolute error would show in log w_min) re-solves with Jacobi.
@@ -297,10 +280,8 @@ __device__ __forceinline__ T pair_value(const TL (&li)[Packed<D>::NP], const T (
       float e2;
       return logsq_series3<float>(a, &e2);
     }
-#ifndef MM_NO_CENTRED
     // pairs at moderate distance (training after the first epochs): the recentred invariants-only series
     if (!__any(centred_far3<float>(a))) return logsq_series3_centred<float>(a);
-#endif
     eig3_trig(a, w);
     const bool wide = !(w[0] * 32.f > w[2]);  // true for NaN / non-positive spectra too
     if (__any(wide)) {
@@ -342,22 +323,18 @@ __device__ __forceinline__ T pair_value(const TL (&li)[Packed<D>::NP], const T (
       }
     } else {
       if (__builtin_expect(!__any(!(close_gate<T, D>(a) <= T(kCloseGate))), 1)) return logsq_series4<T>(a);
-#ifndef MM_NO_CENTRED
       if constexpr (std::is_same<T, float>::value) {   // pairs at moderate distance: the recentred invariants-only series
         if (!__any(centred_far4<T>(a))) return logsq_series4_centred<T>(a);
       }
-#endif
     }
     const T gate = log_cayley<T, D>(a, m0);
     if (__builtin_expect(!__any(!(gate <= T(kCayleyGate))), 1)) return frob2<T, D>(m0);
     T w[D], lw[D], v[D][D];
     return pair_core<T, D, false, CHOL>(li, xj, wmin, wmax, w, lw, v);
-#ifndef MM_SPD2_JACOBI   // (A/B builds: the Jacobi route of rounds 1-4)
   } else if constexpr (D == 2 && CHOL) {
     T mlog[3];   // (closed form, the small eigenvalue from the determinant: smallmat.hpp; the matrix is not needed here)
     return log_pair2_chol<T>(li, xj, wmin, wmax, mlog);
-#endif
-  } else if constexpr (D >= 5 && kSeriesMat) {
+  } else if constexpr (D >= 5) {
     // SPD(5 .. 9): the matrix-Horner series (smallmat.hpp, log_series_mat) for wavefronts of close pairs and of pairs at
     // moderate distance; the eigensolve for the rest
     constexpr int NP = Packed<D>::NP;
@@ -384,14 +361,9 @@ __device__ __forceinline__ T pair_value(const TL (&li)[Packed<D>::NP], const T (
 // scalar loads and the loop's scalar bookkeeping (every instruction of a wavefront, scalar ones included, takes an issue
 // slot of its SIMD) and, in the backward, the row-side reduction (one reduction of M_a + M_b); wider matrices and fp64
 // do not have the registers for it.
-#ifndef MM_SPD2_FWD_NC   // (A/B builds: columns per lane of the SPD(2) kernels)
-#define MM_SPD2_FWD_NC 2
-#endif
-#ifndef MM_SPD2_BWD_NC
-#define MM_SPD2_BWD_NC 2
-#endif
-template <typename T, int D> constexpr int pair_cols() { return (sizeof(T) == 4 && D == 2) ? MM_SPD2_FWD_NC : (sizeof(T) == 4 && D <= 3) ? 2 : ((sizeof(T) == 4 && D == 4) ? MM_SPD4_FWD_NC : 1); }
-template <typename T, int D> constexpr int pair_cols_bwd() { return (sizeof(T) == 4 && D == 3) ? MM_SPD3_BWD_NC : (sizeof(T) == 4 && D == 2) ? MM_SPD2_BWD_NC : ((sizeof(T) == 4 && D == 4) ? MM_SPD4_BWD_NC : 1); }
+constexpr int kSpd2FwdNC = 2, kSpd2BwdNC = 2;   // columns per lane of the SPD(2) kernels
+template <typename T, int D> constexpr int pair_cols() { return (sizeof(T) == 4 && D == 2) ? kSpd2FwdNC : (sizeof(T) == 4 && D <= 3) ? 2 : ((sizeof(T) == 4 && D == 4) ? MM_SPD4_FWD_NC : 1); }
+template <typename T, int D> constexpr int pair_cols_bwd() { return (sizeof(T) == 4 && D == 3) ? MM_SPD3_BWD_NC : (sizeof(T) == 4 && D == 2) ? kSpd2BwdNC : ((sizeof(T) == 4 && D == 4) ? MM_SPD4_BWD_NC : 1); }
 
 // (Round 5: the preparation launch in front of this kernel — spd_prep_kernel, 5 us — cannot be fused into it at a profit.  The row
 // operand must reach the arithmetic as a SCALAR operand: handed over through v_readlane, every vector instruction that reads a
@@ -472,10 +444,8 @@ __global__ __launch_bounds__(kBlock) void spd_pdist_fwd_kernel(const T* __restri
         asm volatile("" : "+v"(joff[q]));
         if (jv[q] > ieff) *reinterpret_cast<T*>(op + joff[q]) = s;
       });
-#ifndef MM_DIAG_STATIC_ROWS   // (diagnostic builds: every row of a tile is stored over its first — the kernel without its HBM stream; wrong results)
       op += ostep;
       ostep -= unsigned(sizeof(T));
-#endif
     }
   }
 }
@@ -558,20 +528,15 @@ __global__ __launch_bounds__((64 * bwd_waves<T, D>()), (bwd_min_waves_nc<T, D, N
   __shared__ T redM[NW][TI][NP];
   __shared__ T colS[NW][NC][D * D][64];
   MM_SPD_STAMP_BEGIN();
-#ifndef MM_DIAG_NO_PRIO
   // (first thing: a wavefront starts at priority 0, and with the older workgroups of its CU in their row loops at 3 the prologue
   // of a late arrival would be served last)
   __builtin_amdgcn_s_setprio(3);
-#endif
   const ColWalk walk(n, row_begin, row_end, 64 * NC);
   // this workgroup's share of the walk, cut on the host (WalkShares): the column block and row it starts at and its budget of
-  // units — one per row, shares.cross per block entered (ColWalk::enter); block-uniform
+  // units — one per row, shares.cross per block entered (ColWalk::enter); block-uniform.  Remembered in the workspace's table from
+  // the first launch of this walk on (rounds 5 and before: computed by every workgroup of every launch)
   int cb, r, rem;
-#ifdef MM_NO_SHARE_TAB   // (A/B builds: the start computed by every workgroup of every launch, as in rounds 5 and before)
-  shares.of(walk, int(blockIdx.x), cb, r, rem);
-#else
   shares.of_cached(walk, int(blockIdx.x), share_tab, cb, r, rem);
-#endif
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform -> row operands stay scalar loads
   bool red_writer;
@@ -590,16 +555,11 @@ __global__ __launch_bounds__((64 * bwd_waves<T, D>()), (bwd_min_waves_nc<T, D, N
   // 40 / 70 / 90 % + 1 row each: with the ~25 rows a wavefront has in the headline launch the third step fell on the last row
   // and the final stretch was the six rows behind the second.  Headline 43.3 -> 42.2 us, SPD(4) n = 2274 27.4 -> 25.6; a fixed
   // four rows for every size cost the 500-row shares of n = 16384 2 %: profiles/r05_experiments.md.)
-#ifndef MM_SPD_PRIO_LAST
-#define MM_SPD_PRIO_LAST 4
-#endif
-  const int prio_last = max(MM_SPD_PRIO_LAST, wave_rows / 10);
+  constexpr int kPrioLast = 4;
+  const int prio_last = max(kPrioLast, wave_rows / 10);
   const int prio_stretch = max(wave_rows - prio_last, 3) / 3;
   int rows_left = prio_stretch;   // rows until the next priority step
-  int phase = 0;
-#ifndef MM_SPD_PRIO_LOOP   // (A/B builds: priority at which the row loop starts; the prologue always runs at 3)
-#define MM_SPD_PRIO_LOOP 3
-#endif
+  int phase = 0;   // (the row loop starts at the prologue's priority, 3)
   // The row reduction leaves one total per lane; NP of the lanes hold distinct entries, the others duplicates.  All
   // lanes store (an exec-masked store costs two scalar instructions per row): writers into redM, advancing by one row
   // per row, the others into a slot of their own that does not move.
@@ -643,13 +603,9 @@ __global__ __launch_bounds__((64 * bwd_waves<T, D>()), (bwd_min_waves_nc<T, D, N
     // leave every TI rows (segments), without restarting the request pipeline.  (Rounds 2-4 cut the rows into chunks of NW x TI
     // and gave every wavefront TI rows of each chunk: every 16 rows a wavefront set its slice up again (~100 scalar
     // instructions), issued its first requests right in front of their use and — vmcnt counts in order — waited behind the
-    // atomics of the flush it had just issued: the memory latency was exposed once per 16 rows.  MM_SPD_BWD_CHUNKED restores
-    // that form for A/B builds; profiles/r05_experiments.md.)  A slice's byte offsets are 32-bit: rows x n x sizeof(T) < 2^31.
-#ifdef MM_SPD_BWD_CHUNKED
-    const int slice_cap = TI;
-#else
+    // atomics of the flush it had just issued: the memory latency was exposed once per 16 rows;
+    // profiles/r05_experiments.md.)  A slice's byte offsets are 32-bit: rows x n x sizeof(T) < 2^31.
     const int slice_cap = max(TI, int(min(int64_t(1) << 20, (int64_t(1) << 31) / (int64_t(n) * int64_t(sizeof(T))))));
-#endif
     while (rem > 0 && r < hi) {   // (one pass, unless the 32-bit cap cuts the block's rows)
       const int chunk = int(min(int64_t(min(hi - r, rem)), int64_t(NW) * slice_cap));
       const int tw = (chunk + NW - 1) / NW;
@@ -668,10 +624,8 @@ __global__ __launch_bounds__((64 * bwd_waves<T, D>()), (bwd_min_waves_nc<T, D, N
         //   use.  Requests are unconditional (a predicated one is an exec-masked branch behind which the compiler waits
         //   for vmcnt(0)) and run kAhead rows ahead into registers that rotate by RENAMING (the loop is unrolled kAhead
         //   times): rotating with moves would wait for the NEWEST request at every row.
-#ifndef MM_SPD_BWD_AHEAD
-#define MM_SPD_BWD_AHEAD 2
-#endif
-        constexpr int kAhead = MM_SPD_BWD_AHEAD;   // (A/B builds: -DMM_SPD_BWD_AHEAD=4)
+        constexpr int kAhead = 2;
+        static_assert(kAhead == 2, "the one padding row of the operand table covers one masked slot: further ahead, clamp roff");
         // SUB: the node of a row comes from the index vector — scalar loads issued one row ahead of their use (the operand
         // table) resp. right behind the previous request (the target row)
         const int first_node = SUB ? __builtin_amdgcn_readfirstlane(batch_node(idx32, size_t(i0), n_total)) : i0;
@@ -708,20 +662,13 @@ __global__ __launch_bounds__((64 * bwd_waves<T, D>()), (bwd_min_waves_nc<T, D, N
               asm volatile("" : "+v"(jslice[q]));   // (see the forward's store: keeps the `v_off, s[ptr]` form inside the loop)
               dst[q] = *reinterpret_cast<const T*>(gslice + goff + jslice[q]);
             });
-#ifndef MM_DIAG_STATIC_ROWS   // (diagnostic builds: every row of a slice reads the slice's first row of g)
             goff = min(goff + gstep, gmax);
             gstep -= unsigned(sizeof(T));
-#endif
           }
         };
-#ifndef MM_DIAG_NO_G
 #pragma unroll
         for (int u = 0; u < kAhead; ++u) request(gq[u]);
-#endif
         MM_SPD_STAMP_MARK(1);
-#if MM_SPD_PRIO_LOOP != 3
-        if (phase == 0) __builtin_amdgcn_s_setprio(MM_SPD_PRIO_LOOP);   // (the prologue ran at 3: a workgroup that arrives outranks the row loops of the older ones)
-#endif
         for (int s0 = i0; s0 < i1; s0 += TI) {   // segments of TI rows: their row sums are staged in LDS and leave together
         const int s1 = min(s0 + TI, i1);
         for (int ib = s0; ib < s1; ib += kAhead) {
@@ -740,7 +687,6 @@ __global__ __launch_bounds__((64 * bwd_waves<T, D>()), (bwd_min_waves_nc<T, D, N
             next_node = __builtin_amdgcn_readfirstlane(batch_node(idx32, size_t(min(irow + 2, n - 1)), n_total));
           } else {
             roff += unsigned(2 * NP * sizeof(T));
-            if constexpr (kAhead > 2) roff = min(roff, unsigned(n) * unsigned(2 * NP * sizeof(T)));   // (more masked slots than the one padding row covers)
           }
           asm volatile("" : "+s"(roff));
           const T* rowp = reinterpret_cast<const T*>(reinterpret_cast<const char*>(nodeLC) + roff);
@@ -749,52 +695,26 @@ __global__ __launch_bounds__((64 * bwd_waves<T, D>()), (bwd_min_waves_nc<T, D, N
           T li[NP], lc[NP];
 #pragma unroll
           for (int k = 0; k < NP; ++k) { li[k] = lcur[k]; lc[k] = lcur[NP + k]; }
-#ifdef MM_DIAG_NO_PRIO
-          if (false) {
-#else
           if (__builtin_expect(--rows_left == 0, 0)) {   // wave-uniform
-#endif
             ++phase;
-#if MM_SPD_PRIO_LOOP == 3
             if (phase == 1) { __builtin_amdgcn_s_setprio(2); rows_left = prio_stretch; }
             else if (phase == 2) { __builtin_amdgcn_s_setprio(1); rows_left = max(wave_rows - prio_last - 2 * prio_stretch, 1); }
             else { __builtin_amdgcn_s_setprio(0); rows_left = INT32_MAX; }
-#else   // (A/B builds: the prologue at 3, the row loop from 2 down — two steps)
-            if (phase == 1) { __builtin_amdgcn_s_setprio(1); rows_left = max(wave_rows - prio_last - 2 * prio_stretch, 1) + prio_stretch; }
-            else { __builtin_amdgcn_s_setprio(0); rows_left = INT32_MAX; }
-#endif
           }
           bool valid[NC];
           T gs[NC], m[NC][NP];
           static_for<NC>([&](auto qc) {
             constexpr int q = decltype(qc)::value;
             valid[q] = jv[q] > ieff;
-#ifdef MM_DIAG_NO_G
-            gs[q] = valid[q] ? T(1) : T(0);
-#else
             gs[q] = valid[q] ? gq[u][q] : T(0);  // upstream gradient (or target) of this row
-#endif
           });
-#ifndef MM_DIAG_NO_G
           request(gq[u]);
-#endif
           // the upstream gradient is known before log(A) unless it depends on the distance (fused loss, d instead of d^2)
           constexpr bool g_first = LOSS == MM_LOSS_NONE && SQ;
           auto jacobi_path = [&](auto qc) __attribute__((always_inline)) {
             constexpr int q = decltype(qc)::value;
-#ifdef MM_DIAG_NO_COLD   // (diagnostic builds, wrong results beyond the gates: what do the cold paths cost the hot one in registers and code?)
-#pragma unroll
-            for (int k = 0; k < NP; ++k) m[q][k] = T(0);
-            return;
-#endif
             T w[D], lw[D], v[D][D];
-#ifdef MM_SPD4_TWO_COL_NO_SECOND   // (A/B builds: the round-4/5 form — no second, one-sided solve in the two-column SPD(4) backward)
-            constexpr int kSecond = (D == 4 && NC == 2) ? 0 : 1;
-#elif defined(MM_SPD4_TWO_COL_INLINE_SECOND)
-            constexpr int kSecond = 1;
-#else
             constexpr int kSecond = (D == 4 && NC == 2) ? 2 : 1;   // two columns: out of line (second_solve_ool)
-#endif
             const T s = pair_core<T, D, true, true, kSecond>(li, xj[q], wmin, wmax, w, lw, v);
             gs[q] = upstream_of<T, LOSS>(gs[q], s, valid[q], squared, wmin, sp, la, loss_acc, ds_acc);
             T cm[D];
@@ -823,11 +743,7 @@ __global__ __launch_bounds__((64 * bwd_waves<T, D>()), (bwd_min_waves_nc<T, D, N
             // What is left (very wide spectra, NaN, non-PD) goes to the Jacobi path.
             T a[NC][NP];
             bool far = false;    // some pair of this row is outside the close-pair gate
-#ifdef MM_NO_CENTRED   // (A/B builds: tools/snap_make.sh nocentred -DMM_NO_CENTRED)
-            constexpr bool kCentred = false;
-#else
-            constexpr bool kCentred = (D == 3 || D == 4) && std::is_same<T, float>::value;
-#endif
+            constexpr bool kCentred = std::is_same<T, float>::value;
             static_for<NC>([&](auto qc) {
               constexpr int q = decltype(qc)::value;
               congr_chol<T, D>(li, xj[q], a[q]);
@@ -873,15 +789,10 @@ __global__ __launch_bounds__((64 * bwd_waves<T, D>()), (bwd_min_waves_nc<T, D, N
               static_for<NC>([&](auto qc) {
                 constexpr int q = decltype(qc)::value;
                 T m0[NP];
-#ifdef MM_DIAG_NO_CAYLEY
-                jacobi_path(qc);
-                return;
-#endif
                 const T gate = log_cayley<T, D>(a[q], m0, g_first ? gs[q] + gs[q] : T(1));
                 if (__builtin_expect(!__any(!(gate <= T(kCayleyGate))), 1)) finish(qc, m0, g_first); else jacobi_path(qc);
               });
             }
-#ifndef MM_SPD2_JACOBI
           } else if constexpr (D == 2) {
             // SPD(2): eigenvalues and logarithm in closed form (smallmat.hpp, log_pair2_chol) — no eigensolve
             static_for<NC>([&](auto qc) {
@@ -893,8 +804,7 @@ __global__ __launch_bounds__((64 * bwd_waves<T, D>()), (bwd_min_waves_nc<T, D, N
 #pragma unroll
               for (int k = 0; k < NP; ++k) m[q][k] = g2 * m0[k];
             });
-#endif
-          } else if constexpr (D >= 5 && kSeriesMat) {
+          } else if constexpr (D >= 5) {
             // SPD(5 .. 9): matrix-Horner series per wavefront (close pairs, pairs at moderate distance), else Jacobi
             static_assert(NC == 1, "one column per lane for D >= 5");
             // (the fp64 SPD(8) backward keeps the eigensolve at moderate distance: 19 products of four spilling 36-entry double
@@ -931,15 +841,11 @@ __global__ __launch_bounds__((64 * bwd_waves<T, D>()), (bwd_min_waves_nc<T, D, N
           });
           // row side: ONE transposing reduction of the lane's NC matrices added up — every lane ends up with the
           // wavefront total of one entry of M
-#ifndef MM_RED_IN_PLACE   // (A/B builds: the round-2..4 form, the second column added into the first one's registers)
           // The columns' sum goes into FRESH registers: added into m[0] in place, every v_permlane*_swap of the reduction's first
           // level got two register copies in front of it (the swap overwrites both operands and the compiler kept m[0] alive) —
           // 12 copies per two rows; headline backward 41.5 -> 40.5 us, mid-training 54.2 -> 51.7, SPD(4) n = 16 384 934 -> 892
           // (profiles/r05_experiments.md section 20).  SPD(2) keeps the in-place form (26.5 against 26.8 us).
           constexpr bool kFreshSums = NC >= 2 && D >= 3;
-#else
-          constexpr bool kFreshSums = false;
-#endif
           if constexpr (kFreshSums) {
           T ms[NP];
 #pragma unroll
@@ -954,11 +860,7 @@ __global__ __launch_bounds__((64 * bwd_waves<T, D>()), (bwd_min_waves_nc<T, D, N
 #pragma unroll
             for (int k = 0; k < NP; ++k) m[0][k] += m[q][k];
           });
-#ifdef MM_DIAG_NO_RED
-          *red_ptr = m[0][0] + m[0][NP - 1];
-#else
           *red_ptr = wave_reduce_transposed<NP, T>(m[0], lane);
-#endif
           }
           red_ptr += red_step;
          }
@@ -969,12 +871,8 @@ __global__ __launch_bounds__((64 * bwd_waves<T, D>()), (bwd_min_waves_nc<T, D, N
         __builtin_amdgcn_wave_barrier();
         for (int t = lane; t < sw * NP; t += 64) {
           const int k = t / sw, il = t - k * sw;
-          {
-            const int node = SUB ? batch_node(idx32, size_t(s0 + il), n_total) : s0 + il;
-#ifndef MM_DIAG_NO_ROW_ATOMICS   // (diagnostic builds, wrong results: what does each part of the row loop's surroundings cost?)
-            atomic_add(&accM[size_t(k) * ns + node], redM[wave][il][k]);
-#endif
-          }
+          const int node = SUB ? batch_node(idx32, size_t(s0 + il), n_total) : s0 + il;
+          atomic_add(&accM[size_t(k) * ns + node], redM[wave][il][k]);
         }
         __builtin_amdgcn_wave_barrier();   // redM is rewritten by the next segment
         }
@@ -1000,11 +898,7 @@ __global__ __launch_bounds__((64 * bwd_waves<T, D>()), (bwd_min_waves_nc<T, D, N
       for (int wv = 1; wv < NW; ++wv) sum += colS[wv][q][k][lane];
       if (j < n) {
         const int node = SUB ? batch_node(idx32, size_t(j), n_total) : j;
-#ifndef MM_DIAG_NO_COL_ATOMICS
         atomic_add(&accS[size_t(k) * ns + node], sum);
-#else
-        if (sum == T(12345.678)) accS[0] = sum;
-#endif
       }
     }
     ++cb;
@@ -1392,10 +1286,7 @@ __global__ void spd_fused_step_kernel(T* x, int n, StepRule<T> rule, StepFuse<T>
   } while (0)
 
 // Threads per workgroup of the per-node kernels (prep, finalize): n = 5000 nodes are 40 workgroups of 128 or 79 of 64
-#ifndef MM_NODE_BLOCK
-#define MM_NODE_BLOCK 128
-#endif
-constexpr int kNodeBlock = MM_NODE_BLOCK;
+constexpr int kNodeBlock = 128;
 template <typename T, int D>
 int spd_pdist_prepare(const T* x, int64_t n, Ws<T>& ws, int flags, hipStream_t st) {
   if (!(flags & MM_WS_PREPARED)) {
@@ -1406,10 +1297,7 @@ int spd_pdist_prepare(const T* x, int64_t n, Ws<T>& ws, int flags, hipStream_t s
   return MM_OK;
 }
 
-#ifndef MM_FWD_TI   // (A/B builds)
-#define MM_FWD_TI 8
-#endif
-constexpr int kFwdTI = MM_FWD_TI;   // rows of a forward tile (sweep on MI355X, SPD(3) fp32, n = 5000: 8 / 16 / 32 rows -> 28.8 / 30.1 / 33.0 us)
+constexpr int kFwdTI = 8;   // rows of a forward tile (sweep on MI355X, SPD(3) fp32, n = 5000: 8 / 16 / 32 rows -> 28.8 / 30.1 / 33.0 us)
 template <typename T, int D, int TI>
 int spd_pdist_fwd_launch(const T* nl, const T* nc, const T* nld, int64_t n, int64_t rb, int64_t re, int squared, double wmin, double wmax,
                          T* out, hipStream_t st) {
