@@ -369,6 +369,36 @@ int mm_grass_pdist_fwd(int dtype, const void* x, int64_t n, int N, int p, int64_
 int mm_grass_pdist_bwd(int dtype, const void* x, const void* g, int64_t n, int N, int p,
                        int64_t row_begin, int64_t row_end, int squared, void* grad_x, void* ws,
                        mm_stream_t stream);
+/* Fused objective + gradients for a single-factor Grassmann embedding — the counterpart of mm_vec_pdist_loss and
+ * mm_spd_pdist_loss (same loss kinds, arguments and outputs; the header comments there apply): with d2 the squared
+ * principal-angle distance of a pair (the p = 2 closed form and its eps clamps included) and m = softplus(*scale_raw) * d2,
+ *   loss_out = { sum of objective(target, m) over the pairs of rows [row_begin, row_end), d loss / d scale_raw },
+ *   grad_x [n,N,p] OVERWRITTEN with this shard's partial gradient (shards sum to the whole).
+ * `target` is the slice of squared graph distances for those rows of the pair list.  One pass over the pairs: every
+ * unordered pair is visited once, its p x p SVD runs once and feeds both of its points (csrc/grass_loss.hip) — no pair
+ * vector is read or written besides `target`.  ws: mm_grass_pdist_loss_ws_bytes(dtype, n, N, p), cleared by the call itself.
+ * Nothing is allocated and nothing synchronises: the call can be captured in a HIP graph.  An empty row range writes a zero
+ * gradient and {0, 0}.  Limits as mm_grass_pdist_bwd (N <= 9, p <= 4, p <= N, n <= 2^30; MM_ERR_ARG / MM_ERR_UNSUPPORTED
+ * before anything touches the GPU; a row range of more than 2^31 - 1 tiles of 16 rows x 64 columns is MM_ERR_UNSUPPORTED).
+ * mm_grass_pdist_loss_form: how (dtype, N, p) walks the pairs — 1: every unordered pair once; 0: ordered pairs (for an
+ * instantiation whose symmetric form would need scratch: none today); < 0: unsupported, with the codes above. */
+size_t mm_grass_pdist_loss_ws_bytes(int dtype, int64_t n, int N, int p);
+int mm_grass_pdist_loss_form(int dtype, int N, int p);
+int mm_grass_pdist_loss(int dtype, int loss_kind, const void* x, const void* target, const void* scale_raw,
+                        int64_t n, int N, int p, int64_t row_begin, int64_t row_end, double alpha, double eps,
+                        int terms, const double* loss_params, void* loss_out, void* grad_x, void* ws,
+                        mm_stream_t stream);
+/* Fused RiemannianSGD update of Grassmann / Stiefel points (rsgd.py:40-82), one launch: rgrad = proju(x, egrad), clipped by
+ * max_grad_norm / sqrt(max(||rgrad||_F^2, 1e-8)) capped at 1 when max_grad_norm > 0, x_new = step(x, -lr * rgrad) with
+ * step = retr_op (MM_MAT_RETR_SVD or MM_MAT_RETR_QR) or, with `exact`, MM_MAT_EXP (Grassmann only: Stiefel returns
+ * MM_ERR_UNSUPPORTED, as mm_mat_map does).  The heavy-ball variant: momentum_buffer = momentum * momentum_buffer +
+ * (1 - dampening) * rgrad, x_new = step(x, -lr * momentum_buffer), and the buffer is transported to x_new
+ * (proju(x_new, .), base.py:65-66) IN PLACE.  x, egrad, momentum_buffer, x_new are [cnt,N,p]; x_new may equal x. */
+int mm_mat_rsgd_step(int dtype, int kind, int retr_op, const void* x, const void* egrad, int64_t cnt, int N, int p,
+                     double lr, double max_grad_norm, int exact, void* x_new, mm_stream_t stream);
+int mm_mat_rsgd_momentum_step(int dtype, int kind, int retr_op, const void* x, const void* egrad,
+                              void* momentum_buffer, int64_t cnt, int N, int p, double lr, double momentum,
+                              double dampening, double max_grad_norm, int exact, void* x_new, mm_stream_t stream);
 
 /* ---- product embeddings ---------------------------------------------------- */
 /* Objective of a product embedding in one pass over the pair vectors (the element-wise part of

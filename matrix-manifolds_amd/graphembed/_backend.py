@@ -116,6 +116,11 @@ SIGNATURES = {
     'mm_grass_pdist_ws_bytes': (_sz, [_i, _i64, _i, _i]),
     'mm_grass_pdist_fwd': (_i, [_i, _vp, _i64, _i, _i, _i64, _i64, _i, _vp, _vp]),
     'mm_grass_pdist_bwd': (_i, [_i, _vp, _vp, _i64, _i, _i, _i64, _i64, _i, _vp, _vp, _vp]),
+    'mm_grass_pdist_loss_ws_bytes': (_sz, [_i, _i64, _i, _i]),
+    'mm_grass_pdist_loss_form': (_i, [_i, _i, _i]),
+    'mm_grass_pdist_loss': (_i, [_i, _i, _vp, _vp, _vp, _i64, _i, _i, _i64, _i64, _dbl, _dbl, _i, _vp, _vp, _vp, _vp, _vp]),
+    'mm_mat_rsgd_step': (_i, [_i, _i, _i, _vp, _vp, _i64, _i, _i, _dbl, _dbl, _i, _vp, _vp]),
+    'mm_mat_rsgd_momentum_step': (_i, [_i, _i, _i, _vp, _vp, _vp, _i64, _i, _i, _dbl, _dbl, _dbl, _dbl, _i, _vp, _vp]),
 }
 GRASSMANN, STIEFEL = 0, 1
 MAT_PROJU, MAT_PROJX, MAT_RETR_SVD, MAT_RETR_QR, MAT_EXP, MAT_LOG = range(6)

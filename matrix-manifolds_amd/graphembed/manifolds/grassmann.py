@@ -71,6 +71,42 @@ class _GrassDist(torch.autograd.Function):
         return gx.reshape(xs), gy.reshape(ys), None, None, None
 
 
+class _GrassPdistLoss(torch.autograd.Function):
+    """loss(target, softplus(scale) * pdist(x)^2) with both gradients from one pass over the
+    pairs (mm_grass_pdist_loss) — see graphembed.manifolds.vector._VecPdistLoss."""
+
+    @staticmethod
+    def forward(ctx, x, scale, target, N, p, spec, row_begin, row_end):
+        B.require_gpu(x, target)
+        lib = B.lib()
+        xc = x.detach().contiguous()
+        n = xc.shape[0]
+        dt = B.dtype_code(xc)
+        lkind, alpha, eps, terms = spec[:4]
+        dyn = spec[4] if len(spec) > 4 else None  # device {alpha, eps} (QuotientLoss.on_device)
+        tc = target.detach().to(xc.dtype).contiguous()
+        npairs = B.pair_offset(n, row_end) - B.pair_offset(n, row_begin)
+        if tc.numel() != npairs:
+            raise ValueError(f'target has {tc.numel()} entries, the pair range has {npairs}')
+        sc = None if scale is None else scale.detach().to(xc.dtype).reshape(1).contiguous()
+        with B.on_device(xc.device):
+            ws = torch.empty(lib.raw('mm_grass_pdist_loss_ws_bytes')(dt, n, N, p), dtype=torch.uint8,
+                             device=xc.device)
+            out = torch.empty(2, dtype=xc.dtype, device=xc.device)
+            grad = torch.empty_like(xc)
+            lib.call('mm_grass_pdist_loss', dt, B.LOSS_STRESS if lkind == 'stress' else B.LOSS_QUOTIENT,
+                     B.ptr(xc), B.ptr(tc), B.ptr(sc), n, N, p, row_begin, row_end, alpha, eps, terms,
+                     B.dyn_ptr(dyn, xc), B.ptr(out), B.ptr(grad), B.ptr(ws), B.stream_of(xc))
+        ctx.grad_x = grad.reshape(x.shape)
+        ctx.grad_s = None if scale is None else out[1].reshape(scale.shape).to(scale.dtype)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, up):
+        gx, gs = B.take_grads(ctx, up, 'grad_x', 'grad_s')
+        return gx, gs, None, None, None, None, None, None
+
+
 class _MatrixManifold(Manifold):
     _kind = None
 
@@ -79,8 +115,10 @@ class _MatrixManifold(Manifold):
         self.p = p
         if retr == 'qr':
             self.retr = self.retr_qr_
+            self._retr_op = B.MAT_RETR_QR
         elif retr == 'svd':
             self.retr = self.retr_svd_
+            self._retr_op = B.MAT_RETR_SVD
         else:
             raise ValueError('Unknown retraction type {}'.format(retr))
 
@@ -124,6 +162,55 @@ class _MatrixManifold(Manifold):
 
     def retr_svd_(self, x, u):
         return self._map(B.MAT_RETR_SVD, x, u)
+
+    def _step_eligible(self, x, egrad, exact, buf=None):
+        """Can the fused optimizer kernels take these tensors?  (GPU, fp32 / fp64, the kernels' sizes, gradient and
+        momentum buffer of the parameter's dtype and shape, contiguous state; Stiefel has no exp.)"""
+        ok = (x.is_cuda and egrad.is_cuda and x.dtype in (torch.float32, torch.float64) and x.numel() > 0
+              and x.ndim >= 2 and tuple(x.shape[-2:]) == (self.n, self.p) and egrad.shape == x.shape
+              and egrad.dtype == x.dtype and not (exact and self._kind == B.STIEFEL))
+        if ok and buf is not None:
+            ok = buf.is_cuda and buf.is_contiguous() and buf.dtype == x.dtype and buf.shape == x.shape
+        if not ok:
+            return False
+        lib = B.lib()
+        return self.n <= lib.raw('mm_mat_max_rows')() and self.p <= lib.raw('mm_mat_max_cols')()
+
+    def rsgd_step(self, x, egrad, *, lr, max_grad_norm=None, exact=False, inplace=False):
+        """Fused momentum-free RiemannianSGD update (optim/rsgd.py:63-68,82) in one launch, with this instance's
+        retraction (or `exp` when `exact`); `inplace=True` writes the new points over `x` (each thread reads its
+        whole point before writing it).  Returns the new points, or None when the tensors are not eligible."""
+        if not self._step_eligible(x, egrad, exact):
+            return None
+        xd = x.detach()
+        inplace = inplace and xd.is_contiguous()
+        xc = xd.reshape(-1, self.n, self.p).contiguous()
+        gc = egrad.detach().reshape(-1, self.n, self.p).contiguous()
+        with B.on_device(xc.device):
+            out = xc if inplace else torch.empty_like(xc)
+            B.lib().call('mm_mat_rsgd_step', B.dtype_code(xc), self._kind, self._retr_op, B.ptr(xc), B.ptr(gc),
+                         xc.shape[0], self.n, self.p, float(lr),
+                         -1.0 if max_grad_norm is None else float(max_grad_norm), int(bool(exact)), B.ptr(out),
+                         B.stream_of(xc))
+        return x if inplace else out.reshape(x.shape)
+
+    def rsgd_momentum_step(self, x, egrad, buf, *, lr, momentum, dampening, max_grad_norm=None, exact=False,
+                           inplace=False):
+        """Fused heavy-ball RiemannianSGD update (optim/rsgd.py:70-80): `buf` (the momentum buffer) is updated and
+        transported in place; returns the new points, or None when the tensors are not eligible."""
+        if not self._step_eligible(x, egrad, exact, buf):
+            return None
+        xd = x.detach()
+        inplace = inplace and xd.is_contiguous()
+        xc = xd.reshape(-1, self.n, self.p).contiguous()
+        gc = egrad.detach().reshape(-1, self.n, self.p).contiguous()
+        with B.on_device(xc.device):
+            out = xc if inplace else torch.empty_like(xc)
+            B.lib().call('mm_mat_rsgd_momentum_step', B.dtype_code(xc), self._kind, self._retr_op, B.ptr(xc),
+                         B.ptr(gc), B.ptr(buf), xc.shape[0], self.n, self.p, float(lr), float(momentum),
+                         float(dampening), -1.0 if max_grad_norm is None else float(max_grad_norm),
+                         int(bool(exact)), B.ptr(out), B.stream_of(xc))
+        return x if inplace else out.reshape(x.shape)
 
     def rand(self, *shape, out=None, ir=1e-2):
         x = self.zero(*shape, out=out)
@@ -176,6 +263,13 @@ class Grassmann(_MatrixManifold):
         assert x.ndim == 3
         rb, re = (0, x.shape[0]) if rows is None else rows
         return _GrassPdist.apply(x, self.n, self.p, squared, rb, re)
+
+    def pdist_loss(self, x, scale, target, spec, rows=None):
+        """Fused `objective(target, softplus(scale) * pdist(x, squared=True))` with its gradients in
+        one pass; `spec` comes from `objective_fn.fused_spec(epoch=, alpha=)`."""
+        assert x.ndim == 3
+        rb, re = (0, x.shape[0]) if rows is None else rows
+        return _GrassPdistLoss.apply(x, scale, target, self.n, self.p, spec, rb, re)
 
     def __str__(self):
         return 'Grassmann manifold of {}x{} matrices'.format(self.n, self.p)

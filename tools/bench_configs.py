@@ -164,6 +164,14 @@ CASES = {
     'sphere6_n5000_f32': lambda: pdist_case(M.Sphere(6), 5000, torch.float32),
     'euclidean10_n5000_f32': lambda: pdist_case(M.Euclidean(10), 5000, torch.float32),
     'grassmann52_n2000_f32': lambda: pdist_case(M.Grassmann(5, 2), 2000, torch.float32),
+    # Grassmann training steps: per-factor objective (pdist forward, loss, pdist backward) | one pair kernel (mm_grass_pdist_loss);
+    # the optimizer update is one launch in all of them (mm_mat_rsgd_step)
+    'grassmann52_step_n2000_f32': lambda: step_case([M.Grassmann(5, 2)], 2000, torch.float32),
+    'grassmann52_step_n2000_f32_fused': lambda: step_case([M.Grassmann(5, 2)], 2000, torch.float32, fused=True),
+    'grassmann52_step_n2000_f32_fused_graph': lambda: step_case([M.Grassmann(5, 2)], 2000, torch.float32, fused=True, graph=True),
+    'grassmann94_step_n2000_f32': lambda: step_case([M.Grassmann(9, 4)], 2000, torch.float32),
+    'grassmann94_step_n2000_f32_fused': lambda: step_case([M.Grassmann(9, 4)], 2000, torch.float32, fused=True),
+    'grassmann94_step_n2000_f32_fused_graph': lambda: step_case([M.Grassmann(9, 4)], 2000, torch.float32, fused=True, graph=True),
 }
 
 
