@@ -400,6 +400,26 @@ int mm_mat_rsgd_momentum_step(int dtype, int kind, int retr_op, const void* x, c
                               void* momentum_buffer, int64_t cnt, int N, int p, double lr, double momentum,
                               double dampening, double max_grad_norm, int exact, void* x_new, mm_stream_t stream);
 
+/* ---- stochastic-neighbour KL objective ---------------------------------------- */
+/* The reference's KLDiveregenceLoss('sne', inclusive) (objectives.py:48-76, inference/stochastic_neighbors.py:8-24) on
+ * pair vectors in this library's order (pair i < j at mm_pair_offset(n, i) + j - i - 1): with
+ *   Z_i(theta) = sum_{j != i} exp theta_ij,  A(theta) = sum_i log Z_i,  P_ij(theta) = exp(theta_ij) / Z_i,
+ *   loss = A(theta_z) - A(theta_x) - sum_{i<j} (P_ij + P_ji)(theta_x) (theta_z - theta_x)_ij  = sum_i KL(P_i(theta_x) || P_i(theta_z)),
+ *   MM_SNE_INCLUSIVE: theta_x = -alpha * target, theta_z = -m;   MM_SNE_EXCLUSIVE: theta_x = -m, theta_z = -alpha * target.
+ * target, m: [n (n - 1) / 2] squared graph / manifold distances.  loss_out[0] = loss (one value of `dtype`); grad_out, when
+ * not null, is OVERWRITTEN with d loss / d m, one value per pair.  Three passes (csrc/sne_loss.hip): per-tile node
+ * statistics with a per-node shift of the exponentials, a per-node merge, the gradient (skipped when grad_out is null);
+ * no n x n array and no float atomics, so the results are bitwise reproducible from call to call.
+ * ws: mm_sne_kl_ws_bytes(dtype, n) bytes (0 for an unknown dtype, n < 0 or n above the limit); it needs no clearing.
+ * Nothing is allocated and nothing synchronises: the call can be captured in a HIP graph.
+ * MM_ERR_ARG for an unknown dtype or mode, n < 0, a null loss_out and, for n >= 2, a null target, m or ws — before anything
+ * touches the GPU.  n < 2: loss_out[0] = 0, nothing else is read or written.  n > 32768 returns MM_ERR_UNSUPPORTED (pair
+ * offsets stay below 2^31 elements up to there, and the fp64 workspace is 0.8 GB at the limit). */
+enum { MM_SNE_INCLUSIVE = 0, MM_SNE_EXCLUSIVE = 1 };
+size_t mm_sne_kl_ws_bytes(int dtype, int64_t n);
+int mm_sne_kl_loss(int dtype, int mode, const void* target, const void* m, int64_t n, double alpha,
+                   void* grad_out /* may be null */, void* loss_out, void* ws, mm_stream_t stream);
+
 /* ---- product embeddings ---------------------------------------------------- */
 /* Objective of a product embedding in one pass over the pair vectors (the element-wise part of
  * train.py:213-217 for several factors): with d2[k] the squared pair distances of factor k,

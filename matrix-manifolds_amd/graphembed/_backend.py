@@ -119,10 +119,13 @@ SIGNATURES = {
     'mm_grass_pdist_loss_ws_bytes': (_sz, [_i, _i64, _i, _i]),
     'mm_grass_pdist_loss_form': (_i, [_i, _i, _i]),
     'mm_grass_pdist_loss': (_i, [_i, _i, _vp, _vp, _vp, _i64, _i, _i, _i64, _i64, _dbl, _dbl, _i, _vp, _vp, _vp, _vp, _vp]),
+    'mm_sne_kl_ws_bytes': (_sz, [_i, _i64]),
+    'mm_sne_kl_loss': (_i, [_i, _i, _vp, _vp, _i64, _dbl, _vp, _vp, _vp, _vp]),
     'mm_mat_rsgd_step': (_i, [_i, _i, _i, _vp, _vp, _i64, _i, _i, _dbl, _dbl, _i, _vp, _vp]),
     'mm_mat_rsgd_momentum_step': (_i, [_i, _i, _i, _vp, _vp, _vp, _i64, _i, _i, _dbl, _dbl, _dbl, _dbl, _i, _vp, _vp]),
 }
 GRASSMANN, STIEFEL = 0, 1
+SNE_INCLUSIVE, SNE_EXCLUSIVE = 0, 1  # MM_SNE_*
 MAT_PROJU, MAT_PROJX, MAT_RETR_SVD, MAT_RETR_QR, MAT_EXP, MAT_LOG = range(6)
 VEC_EGRAD2RGRAD, VEC_PROJU, VEC_EXP, VEC_RETR, VEC_PROJX, VEC_TRANSP, VEC_LOG = range(7)
 

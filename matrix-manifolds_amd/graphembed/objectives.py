@@ -1,10 +1,13 @@
 """Losses on vectors of *squared* distances used by the path's configs —
 counterparts of graphembed/graphembed/objectives.py:16-45 (Stress, Quotient).
-PearsonRLoss runs on the differentiable pdist path; the KL / curvature losses (inference models, graph
-sampling) are outside the accelerated path."""
+PearsonRLoss runs on the differentiable pdist path.  StochasticNeighborLoss is the reference's
+KLDiveregenceLoss('sne', inclusive) (objectives.py:48-76) on the kernels of csrc/sne_loss.hip; the spanning-tree
+model ('sste') and the curvature regulariser (graph sampling) are outside the accelerated path."""
 import abc
+import math
 
 import torch
+from torch.autograd.function import once_differentiable
 
 
 class ObjectiveFunction:
@@ -123,6 +126,98 @@ class PearsonRLoss(ObjectiveFunction):
 
     def __str__(self):
         return 'pearson_r_loss'
+
+
+def _nodes_of(npairs):
+    """n with n (n - 1) / 2 == npairs (1 for an empty pair vector)."""
+    n = (1 + math.isqrt(1 + 8 * npairs)) // 2
+    if n * (n - 1) // 2 != npairs:
+        raise ValueError(f'a pair vector has n (n - 1) / 2 entries; {npairs} is not such a number')
+    return n
+
+
+class _SneKL(torch.autograd.Function):
+    """Loss and d loss / d mdists from one C-ABI call (mm_sne_kl_loss): statistics, merge and — only when `mdists`
+    requires a gradient — the gradient pass."""
+
+    @staticmethod
+    def forward(ctx, gdists, mdists, mode, alpha):
+        from graphembed import _backend as B
+        B.require_gpu(gdists, mdists)
+        lib = B.lib()
+        n = _nodes_of(mdists.numel())
+        m = mdists.detach().contiguous()
+        g = gdists.detach().to(dtype=m.dtype, device=m.device).contiguous()
+        if g.numel() != m.numel():
+            raise ValueError(f'target has {g.numel()} entries, the pair vector has {m.numel()}')
+        dt = B.dtype_code(m)
+        with B.on_device(m.device):
+            grad = torch.empty_like(m) if ctx.needs_input_grad[1] else None
+            out = torch.empty(1, dtype=m.dtype, device=m.device)
+            ws = torch.empty(lib.raw('mm_sne_kl_ws_bytes')(dt, n), dtype=torch.uint8, device=m.device)
+            lib.call('mm_sne_kl_loss', dt, mode, B.ptr(g), B.ptr(m), n, float(alpha), B.ptr(grad), B.ptr(out), B.ptr(ws),
+                     B.stream_of(m))
+        ctx.grad = None if grad is None else grad.view(mdists.shape)
+        return out[0]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, up):
+        from graphembed import _backend as B
+        return (None, B.take_grads(ctx, up, 'grad')[0], None, None)
+
+
+class StochasticNeighborLoss(ObjectiveFunction):
+    """sum_i KL(P_i(theta_x) || P_i(theta_z)) of the stochastic-neighbour model P_ij(theta) = exp(theta_ij) / sum_k exp(theta_ik)
+    over pair vectors — inclusive: theta_x = -alpha g, theta_z = -m; exclusive: swapped (objectives.py:48-76 with
+    inference/stochastic_neighbors.py:8-24).  `alpha` is a plain float and has no gradient.
+
+    GPU tensors go through the kernels of csrc/sne_loss.hip (no n x n array, bitwise reproducible); CPU tensors, or
+    `native=False`, evaluate the same loss with torch ops on a dense [n, n] theta — differentiable by autograd.  There is no
+    `fused_spec`: BatchedObjective feeds it `compute_dists`, so it serves every manifold, product and node minibatch.  A node's
+    partition function needs its whole row, so the row-sharded evaluation of graphembed.parallel is not offered."""
+
+    def __init__(self, inclusive=True, native=True):
+        self.inclusive = inclusive
+        self.native = native
+
+    def __call__(self, gdists, mdists, *, epoch=None, alpha):
+        n = _nodes_of(mdists.numel())
+        if gdists.numel() != mdists.numel():
+            raise ValueError(f'target has {gdists.numel()} entries, the pair vector has {mdists.numel()}')
+        if self.native and mdists.is_cuda:
+            from graphembed import _backend as B
+            return _SneKL.apply(gdists, mdists, B.SNE_INCLUSIVE if self.inclusive else B.SNE_EXCLUSIVE, float(alpha))
+        return self._torch_ops(gdists, mdists, n, alpha)
+
+    def _torch_ops(self, gdists, mdists, n, alpha):
+        if n < 2:
+            return mdists.sum() * 0
+        theta_x, theta_z = -alpha * gdists.to(mdists.dtype), -mdists
+        if not self.inclusive:
+            theta_x, theta_z = theta_z, theta_x
+        iu = torch.triu_indices(n, n, 1, device=mdists.device)
+
+        def dense(theta, diagonal):
+            full = theta.new_full((n, n), diagonal)
+            return full.index_put((torch.cat([iu[0], iu[1]]), torch.cat([iu[1], iu[0]])), torch.cat([theta, theta]))
+
+        def log_partition(full):
+            # logsumexp of the rows, each shifted by its own (constant) maximum first: its backward, exp(theta - result), then
+            # equals the softmax below to an ulp of 1 instead of an ulp of |theta| — the two cancel in d loss / d theta_x
+            shift = full.detach().max(dim=1, keepdim=True).values
+            return (shift[:, 0] + torch.logsumexp(full - shift, dim=1)).sum()
+
+        dx, dz = dense(theta_x, -math.inf), dense(theta_z, -math.inf)
+        p = torch.softmax(dx, dim=1)
+        # sum_j P_ij delta_ij as sum_j P_ij (delta_ij - c_i) + c_i with the constant c_i = mu_i (the rows of P sum to 1): the
+        # softmax backward then forms P (delta - mu) from small numbers, not as the difference of two sums of size |delta|
+        delta = dense(theta_z - theta_x, 0.0)
+        mu = (p * delta).sum(dim=1, keepdim=True).detach()
+        return log_partition(dz) - log_partition(dx) - (p * (delta - mu)).sum() - mu.sum()
+
+    def __str__(self):
+        return 'kl_loss'
 
 
 class Sum(ObjectiveFunction):

@@ -14,7 +14,7 @@ import torch  # noqa: E402
 from graphembed import manifolds as M  # noqa: E402
 from graphembed._backend import unit_seed  # noqa: E402
 from graphembed.modules import ManifoldEmbedding  # noqa: E402
-from graphembed.objectives import StressLoss  # noqa: E402
+from graphembed.objectives import StochasticNeighborLoss, StressLoss  # noqa: E402
 from graphembed.optim import RiemannianAdam, RiemannianSGD  # noqa: E402
 
 
@@ -57,8 +57,9 @@ def native_case(mans, n, dtype, loss='stress'):
     return {'n': n, 'pairs': P, 'dtype': str(dtype).split('.')[-1], 'step_us': t, 'pairs_per_s': P / (t * 1e-6)}
 
 
-def step_case(mans, n, dtype, fused=False, graph=False, pair_kernel=True, adam=False):
-    """full training step: compute_dists + stress loss + backward + fused RSGD (momentum 0)"""
+def step_case(mans, n, dtype, fused=False, graph=False, pair_kernel=True, adam=False, sne=None, native=True):
+    """full training step: compute_dists + stress loss + backward + fused RSGD (momentum 0); `sne` = 'incl' / 'excl': the
+    stochastic-neighbour KL loss instead (alpha = 1), on its kernels or, `native=False`, in its torch-op form"""
     torch.manual_seed(0)
     torch.set_default_dtype(dtype)
     try:
@@ -69,7 +70,8 @@ def step_case(mans, n, dtype, fused=False, graph=False, pair_kernel=True, adam=F
         torch.set_default_dtype(torch.float32)
     P = n * (n - 1) // 2
     target = torch.rand(P, dtype=dtype, device='cuda') * 0.99 + 0.01
-    fn = StressLoss()
+    fn = StressLoss() if sne is None else StochasticNeighborLoss(inclusive=sne == 'incl', native=native)
+    kw = {} if sne is None else {'alpha': 1.0}
     if adam:  # the optimizer of the paper grid (experiments/run_grid.py:24-36)
         opt = RiemannianAdam(list(emb.xs), lr=1e-3, exact=True, max_grad_norm=20)
         opt_s = RiemannianAdam(list(emb.scales), lr=1e-4, max_grad_norm=500)
@@ -80,7 +82,7 @@ def step_case(mans, n, dtype, fused=False, graph=False, pair_kernel=True, adam=F
     def step():
         opt.zero_grad(set_to_none=True)
         opt_s.zero_grad(set_to_none=True)
-        loss = emb.fused_objective(fn, target, None) if fused else fn(target, emb.compute_dists(None))
+        loss = emb.fused_objective(fn, target, None) if fused else fn(target, emb.compute_dists(None), **kw)
         loss.backward(unit_seed(loss))
         opt.step()
         opt_s.step()
@@ -172,6 +174,14 @@ CASES = {
     'grassmann94_step_n2000_f32': lambda: step_case([M.Grassmann(9, 4)], 2000, torch.float32),
     'grassmann94_step_n2000_f32_fused': lambda: step_case([M.Grassmann(9, 4)], 2000, torch.float32, fused=True),
     'grassmann94_step_n2000_f32_fused_graph': lambda: step_case([M.Grassmann(9, 4)], 2000, torch.float32, fused=True, graph=True),
+    # stochastic-neighbour KL loss (StochasticNeighborLoss: pdist forward, mm_sne_kl_loss, pdist backward) | its torch-op form
+    'c3_spd3_sne_incl_step_n5000_f32': lambda: step_case([M.SymmetricPositiveDefinite(3)], 5000, torch.float32, sne='incl'),
+    'c3_spd3_sne_incl_step_n5000_f32_torchops': lambda: step_case([M.SymmetricPositiveDefinite(3)], 5000, torch.float32, sne='incl', native=False),
+    'c3_spd3_sne_incl_step_n5000_f32_graph': lambda: step_case([M.SymmetricPositiveDefinite(3)], 5000, torch.float32, sne='incl', graph=True),
+    'c3_spd3_sne_excl_step_n5000_f32': lambda: step_case([M.SymmetricPositiveDefinite(3)], 5000, torch.float32, sne='excl'),
+    'c3_spd3_sne_excl_step_n5000_f32_torchops': lambda: step_case([M.SymmetricPositiveDefinite(3)], 5000, torch.float32, sne='excl', native=False),
+    'c3_spd3_sne_excl_step_n5000_f32_graph': lambda: step_case([M.SymmetricPositiveDefinite(3)], 5000, torch.float32, sne='excl', graph=True),
+    'c4_csphd_sne_incl_step_f32_graph': lambda: step_case([M.Lorentz(6), M.Sphere(6), M.SymmetricPositiveDefinite(2)], 1025, torch.float32, sne='incl', graph=True),
 }
 
 
