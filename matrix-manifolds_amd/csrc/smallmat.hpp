@@ -615,29 +615,34 @@ template <typename T> __device__ __forceinline__ T log_series3(const T (&a)[6], 
   using S = LogSeries<T>;
   const T e00 = a[pidx(0, 0)] - T(1), e11 = a[pidx(1, 1)] - T(1), e22 = a[pidx(2, 2)] - T(1);
   const T e10 = a[pidx(1, 0)], e20 = a[pidx(2, 0)], e21 = a[pidx(2, 1)];
-  // E^2 (symmetric)
+  // diagonal of E^2: the close-pair gate's own three sums (close_gate, spd_pair.hpp — the same expressions, so a caller
+  // that has evaluated the gate pays for them once)
   const T f00 = N::fma(e00, e00, N::fma(e10, e10, e20 * e20));
   const T f11 = N::fma(e10, e10, N::fma(e11, e11, e21 * e21));
   const T f22 = N::fma(e20, e20, N::fma(e21, e21, e22 * e22));
-  const T f10 = N::fma(e10, e00, N::fma(e11, e10, e21 * e20));
-  const T f20 = N::fma(e20, e00, N::fma(e21, e10, e22 * e20));
-  const T f21 = N::fma(e20, e10, N::fma(e21, e11, e22 * e21));
   const T tr2 = f00 + f11 + f22;                      // ||E||_F^2
+  // The off-diagonal of E^2 is NOT formed.  adj(E) = E^2 - s1 E + s2 I, so off the diagonal E^2 = adj(E) + s1 E: the three
+  // off-diagonal cofactors (two operations each, against three for an entry of E^2) serve the result AND the determinant,
+  // s3 = e00 c00 + e10 c10 + e20 c20 — one more cofactor instead of three separate minors.
+  const T c00 = N::fma(e11, e22, -e21 * e21);
+  const T c10 = N::fma(e21, e20, -e10 * e22);
+  const T c20 = N::fma(e10, e21, -e11 * e20);
+  const T c21 = N::fma(e10, e20, -e00 * e21);
   const T s1 = e00 + e11 + e22;
   const T s2 = T(0.5) * N::fma(s1, s1, -tr2);
-  const T s3 = e00 * N::fma(e11, e22, -e21 * e21) - e10 * N::fma(e10, e22, -e21 * e20) +
-               e20 * N::fma(e10, e21, -e11 * e20);
+  const T s3 = N::fma(e20, c20, N::fma(e10, c10, e00 * c00));
   // Horner from the top: after the first two steps alpha = (c_{n-3}, c_{n-2}, c_{n-1})
   T a0, a1, a2;
   ring_horner3<T, S>(s1, s2, s3, a0, a1, a2);
   // log(I + E) = E p(E): one more multiplication by E (no constant), then the caller's factor
   const T b0 = (a2 * s3) * pre, b1 = N::fma(-a2, s2, a0) * pre, b2 = N::fma(a2, s1, a1) * pre;
+  const T k1 = N::fma(b2, s1, b1);                    // off the diagonal: b1 E + b2 E^2 = (b1 + b2 s1) E + b2 adj(E)
   m0[pidx(0, 0)] = N::fma(b2, f00, N::fma(b1, e00, b0));
   m0[pidx(1, 1)] = N::fma(b2, f11, N::fma(b1, e11, b0));
   m0[pidx(2, 2)] = N::fma(b2, f22, N::fma(b1, e22, b0));
-  m0[pidx(1, 0)] = N::fma(b2, f10, b1 * e10);
-  m0[pidx(2, 0)] = N::fma(b2, f20, b1 * e20);
-  m0[pidx(2, 1)] = N::fma(b2, f21, b1 * e21);
+  m0[pidx(1, 0)] = N::fma(b2, c10, k1 * e10);
+  m0[pidx(2, 0)] = N::fma(b2, c20, k1 * e20);
+  m0[pidx(2, 1)] = N::fma(b2, c21, k1 * e21);
   return tr2;
 }
 
@@ -698,25 +703,24 @@ template <typename T> __device__ __forceinline__ void log_series3_centred(const 
   const T rmu = N::rcp(mu);
   const T e00 = N::fma(a[pidx(0, 0)], rmu, T(-1)), e11 = N::fma(a[pidx(1, 1)], rmu, T(-1)), e22 = N::fma(a[pidx(2, 2)], rmu, T(-1));
   const T e10 = a[pidx(1, 0)] * rmu, e20 = a[pidx(2, 0)] * rmu, e21 = a[pidx(2, 1)] * rmu;
-  const T f00 = N::fma(e00, e00, N::fma(e10, e10, e20 * e20));
-  const T f11 = N::fma(e10, e10, N::fma(e11, e11, e21 * e21));
-  const T f22 = N::fma(e20, e20, N::fma(e21, e21, e22 * e22));
-  const T f10 = N::fma(e10, e00, N::fma(e11, e10, e21 * e20));
-  const T f20 = N::fma(e20, e00, N::fma(e21, e10, e22 * e20));
-  const T f21 = N::fma(e20, e10, N::fma(e21, e11, e22 * e21));
-  const T s2 = T(-0.5) * (f00 + f11 + f22);          // s1 = 0: s2 = -tr(E'^2) / 2
-  const T s3 = e00 * N::fma(e11, e22, -e21 * e21) - e10 * N::fma(e10, e22, -e21 * e20) +
-               e20 * N::fma(e10, e21, -e11 * e20);
+  // E'^2 is not formed: adj(E') = E'^2 - s1 E' + s2 I with s1 = 0, so b2 E'^2 = b2 adj(E') - b2 s2 I.  The six cofactors are
+  // two operations each (an entry of E'^2: three), three of them are the minors of det E', and their trace is s2 — a plain
+  // sum, where -tr(E'^2) / 2 needed the whole of E'^2's diagonal
+  const T c00 = N::fma(e11, e22, -e21 * e21), c11 = N::fma(e00, e22, -e20 * e20), c22 = N::fma(e00, e11, -e10 * e10);
+  const T c10 = N::fma(e21, e20, -e10 * e22), c20 = N::fma(e10, e21, -e11 * e20), c21 = N::fma(e10, e20, -e00 * e21);
+  const T s2 = c00 + c11 + c22;
+  const T s3 = N::fma(e20, c20, N::fma(e10, c10, e00 * c00));
   T a0, a1, a2;
   ring_horner3<T, S, true>(T(0), s2, s3, a0, a1, a2);
   const T logmu = N::log(mu);
-  const T b0 = N::fma(a2, s3, logmu) * pre, b1 = N::fma(-a2, s2, a0) * pre, b2 = a1 * pre;
-  m0[pidx(0, 0)] = N::fma(b2, f00, N::fma(b1, e00, b0));
-  m0[pidx(1, 1)] = N::fma(b2, f11, N::fma(b1, e11, b0));
-  m0[pidx(2, 2)] = N::fma(b2, f22, N::fma(b1, e22, b0));
-  m0[pidx(1, 0)] = N::fma(b2, f10, b1 * e10);
-  m0[pidx(2, 0)] = N::fma(b2, f20, b1 * e20);
-  m0[pidx(2, 1)] = N::fma(b2, f21, b1 * e21);
+  const T b1 = N::fma(-a2, s2, a0) * pre, b2 = a1 * pre;
+  const T b0 = N::fma(-b2, s2, N::fma(a2, s3, logmu) * pre);
+  m0[pidx(0, 0)] = N::fma(b2, c00, N::fma(b1, e00, b0));
+  m0[pidx(1, 1)] = N::fma(b2, c11, N::fma(b1, e11, b0));
+  m0[pidx(2, 2)] = N::fma(b2, c22, N::fma(b1, e22, b0));
+  m0[pidx(1, 0)] = N::fma(b2, c10, b1 * e10);
+  m0[pidx(2, 0)] = N::fma(b2, c20, b1 * e20);
+  m0[pidx(2, 1)] = N::fma(b2, c21, b1 * e21);
 }
 
 // d^2 = ||log A||_F^2 of a pair at moderate distance, straight from invariants (the forward's counterpart of
@@ -784,7 +788,8 @@ template <> __device__ __forceinline__ double ldexp_t<double>(double x, int k) {
 //            = b0 + b1 Z + b2 Z^2      (c0 Z + c1 Z^3 + c2 Z^5 reduced in R[Z]/(chi_Z): three steps of three FMAs),
 //            = g0 + g1 E + g2 E^2      (Z, Z^2 written in the E basis by ring arithmetic on their coefficients),
 //   log A = log(mu) I + 2 (g0 I + g1 E + g2 E^2).
-// Matrix work: E^2 (18 FMAs) and the last line (12) — against the adjugate, three commuting 3x3 products and the assembly
+// Matrix work: adj(E) (12 operations; E^2 = adj(E) + s1 E - s2 I is never formed: the cofactors are s3's minors and their
+// trace is s2) and the last line (12 + 2) — against the adjugate, three commuting 3x3 products and the assembly
 // of P(W) (~105) of the round-1..3 form; ~146 operations in all against ~180, six matrix temporaries fewer alive, and the
 // gate tr(Z^2) is known before any matrix is formed.  Accuracy (emulated, against a 40-digit eigendecomposition): 5e-7
 // of max|log A| in fp32, 7e-15 in fp64, spectra of any spread inside the gate and mu up to 2^+-11.
@@ -855,16 +860,13 @@ template <typename T> __device__ __forceinline__ T log_cayley3(const T (&a)[6], 
   const T r = cayley_scale<T>((a[0] + a[2] + a[5]) * T(1.0 / 3.0), &logmu);
   const T e00 = N::fma(a[0], r, T(-1)), e11 = N::fma(a[2], r, T(-1)), e22 = N::fma(a[5], r, T(-1));
   const T e10 = a[1] * r, e20 = a[3] * r, e21 = a[4] * r;
-  const T f00 = N::fma(e00, e00, N::fma(e10, e10, e20 * e20));
-  const T f11 = N::fma(e10, e10, N::fma(e11, e11, e21 * e21));
-  const T f22 = N::fma(e20, e20, N::fma(e21, e21, e22 * e22));
-  const T f10 = N::fma(e10, e00, N::fma(e11, e10, e21 * e20));
-  const T f20 = N::fma(e20, e00, N::fma(e21, e10, e22 * e20));
-  const T f21 = N::fma(e20, e10, N::fma(e21, e11, e22 * e21));
+  // adj(E) in place of E^2 (E^2 = adj(E) + s1 E - s2 I): six cofactors of two operations, three of them the minors of
+  // s3, their trace s2 without the cancellation of (s1^2 - tr E^2) / 2
+  const T c00 = N::fma(e11, e22, -e21 * e21), c11 = N::fma(e00, e22, -e20 * e20), c22 = N::fma(e00, e11, -e10 * e10);
+  const T c10 = N::fma(e21, e20, -e10 * e22), c20 = N::fma(e10, e21, -e11 * e20), c21 = N::fma(e10, e20, -e00 * e21);
   const T s1 = e00 + e11 + e22;
-  const T s2 = T(0.5) * N::fma(s1, s1, -(f00 + f11 + f22));
-  const T s3 = e00 * N::fma(e11, e22, -e21 * e21) - e10 * N::fma(e10, e22, -e21 * e20) +
-               e20 * N::fma(e10, e21, -e11 * e20);
+  const T s2 = c00 + c11 + c22;
+  const T s3 = N::fma(e20, c20, N::fma(e10, c10, e00 * c00));
   T rD, z1, z2, z3, t1, t2, t3;
   cayley3_spectrum<T>(s1, s2, s3, rD, z1, z2, z3, t1, t2, t3);
   // P(W) = c0 + c1 W + c2 W^2 by Horner in R[W]/(chi_W), W^3 = t1 W^2 - t2 W + t3 I
@@ -896,12 +898,14 @@ template <typename T> __device__ __forceinline__ T log_cayley3(const T (&a)[6], 
   const T g0 = N::fma(N::fma(b2, w0, N::fma(b1, y0, b0)), p2, logmu * pre);
   const T g1 = N::fma(b2, w1, b1 * y1) * p2;
   const T g2 = N::fma(b2, w2, b1 * y2) * p2;
-  m0[0] = N::fma(g2, f00, N::fma(g1, e00, g0));
-  m0[2] = N::fma(g2, f11, N::fma(g1, e11, g0));
-  m0[5] = N::fma(g2, f22, N::fma(g1, e22, g0));
-  m0[1] = N::fma(g2, f10, g1 * e10);
-  m0[3] = N::fma(g2, f20, g1 * e20);
-  m0[4] = N::fma(g2, f21, g1 * e21);
+  // g0 I + g1 E + g2 E^2 = (g0 - g2 s2) I + (g1 + g2 s1) E + g2 adj(E)
+  const T k0 = N::fma(-g2, s2, g0), k1 = N::fma(g2, s1, g1);
+  m0[0] = N::fma(g2, c00, N::fma(k1, e00, k0));
+  m0[2] = N::fma(g2, c11, N::fma(k1, e11, k0));
+  m0[5] = N::fma(g2, c22, N::fma(k1, e22, k0));
+  m0[1] = N::fma(g2, c10, k1 * e10);
+  m0[3] = N::fma(g2, c20, k1 * e20);
+  m0[4] = N::fma(g2, c21, k1 * e21);
   return t1;
 }
 

@@ -421,6 +421,14 @@ __global__ __launch_bounds__(kBlock) void spd_pdist_fwd_kernel(const T* __restri
 #pragma unroll
   for (int k = 0; k < NP; ++k) lrow[0][k] = nodeL[size_t(i0) * NP + k];
   if constexpr (kLd) ldrow[0] = nodeLd[i0];
+  // An INTERIOR wavefront — its first column above the tile's last row, its last column inside n, an even number of rows (no
+  // masked second slot) — stores every lane of every row: `jv > ieff` is true throughout, and the exec-masked store it guards
+  // (a compare, a saveexec, a branch and a restore per pair) is most of what the loop spends outside the arithmetic.  Most of a
+  // launch is interior (all wavefronts of a tile but the one or two on the diagonal and the one on a ragged last column block),
+  // so the row loop exists twice and a wavefront picks one on a wave-uniform flag, once.
+  const bool interior = wave_j0 >= i1 && wave_j0 + 64 * NC <= n && ((i1 - i0) & 1) == 0;
+  auto row_loop = [&](auto masked_c) __attribute__((always_inline)) {
+  constexpr bool kMasked = decltype(masked_c)::value;
   for (int ib = i0; ib < i1; ib += 2) {
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
@@ -442,12 +450,14 @@ __global__ __launch_bounds__(kBlock) void spd_pdist_fwd_kernel(const T* __restri
         // (re-defined in this block: a zero-extension hoisted out of the loop hides from instruction selection that the
         // lane offset is 32 bits wide, and the store gets a 64-bit vector address instead of `v_off, s[ptr]`)
         asm volatile("" : "+v"(joff[q]));
-        if (jv[q] > ieff) *reinterpret_cast<T*>(op + joff[q]) = s;
+        if (!kMasked || jv[q] > ieff) *reinterpret_cast<T*>(op + joff[q]) = s;
       });
       op += ostep;
       ostep -= unsigned(sizeof(T));
     }
   }
+  };
+  if (interior) row_loop(std::false_type{}); else row_loop(std::true_type{});
 }
 
 // The value loaded from the pair vector is the upstream gradient (LOSS == 0: of d2, or of d when
