@@ -420,6 +420,68 @@ size_t mm_sne_kl_ws_bytes(int dtype, int64_t n);
 int mm_sne_kl_loss(int dtype, int mode, const void* target, const void* m, int64_t n, double alpha,
                    void* grad_out /* may be null */, void* loss_out, void* ws, mm_stream_t stream);
 
+/* ---- constant curvature: the kappa-stereographic model ------------------------ */
+/* The reference's `Universal` manifold (manifolds/universal.py, manifolds/impl/math.py): the Poincare ball for c > 0, the
+ * stereographic projection of the sphere for c < 0, curvature K = -c, with c a TRAINABLE parameter.  Points are rows of
+ * x [n, m], 1 <= m <= 16.  The curvature is passed as (c_raw, c_mode, c_min): c_raw is ONE element of `dtype` in DEVICE
+ * memory, and the kernels apply get_c (universal.py:27-31) themselves,
+ *   MM_STEREO_C_FREE      c = sign(c_raw) c_min + c_raw                 (keep_sign_fixed = False)
+ *   MM_STEREO_C_POSITIVE  c =   c_min + softplus(c_raw)                  (keep_sign_fixed, c_init > 0)
+ *   MM_STEREO_C_NEGATIVE  c = -(c_min + softplus(c_raw))                 (keep_sign_fixed, c_init < 0)
+ * so a captured graph follows the optimizer's updates of c_raw without re-capture and the host never reads c.
+ * Curvature gradients are with respect to c_raw (chain rule applied in the kernel).
+ *
+ * Distance (csrc/stereo.hip has the derivation): with q = |x_i - x_j|^2, D = (1 - c|x_i|^2)(1 - c|x_j|^2) + c q, t = q / D,
+ *   d = 2 sqrt(t) phi(c t),  phi(w) = artanh(sqrt w)/sqrt w (w > 0), atan(sqrt -w)/sqrt -w (w < 0), phi(0) = 1,
+ * the value clamped at 1e-8 after squaring (universal.py:79-84; the clamp is transparent to the gradient), D at 1e-15
+ * (impl/math.py:345).  phi is one analytic function: c = 0 EXACTLY gives the Euclidean limit d^2 = 4 q, where the
+ * reference returns NaN.
+ *
+ * mm_stereo_pdist_fwd / _bwd: pair vector in the row-range layout described at the top.  grad_x [n, m] and grad_c [1] are
+ * OVERWRITTEN with this shard's partial gradients; an empty row range leaves zeros; n < 2 writes nothing but a zero
+ * grad_c.  Every unordered pair is visited once, nothing is accumulated with float atomics (results are bitwise
+ * reproducible), the curvature gradient is summed in fp64.  ws: mm_stereo_pdist_ws_bytes(dtype, n, m) bytes (0 for
+ * arguments the library refuses); it needs no clearing.  It holds one record of m + 1 values per node and tile row /
+ * tile column: 4 (m + 1) n (ceil(n / 64) * 2) bytes in fp32, 8 (m + 1) n (ceil(n / 32) + ceil(n / 64)) in fp64 — 23 MB
+ * at n = 4039, m = 10 in fp32, 2.3 GB (fp32) / 6.8 GB (fp64) at the node limit with m = 16 — plus 8 bytes per tile.
+ * mm_stereo_dist: element-wise over cnt pairs (x[k], y[k]); out may be NULL (backward only); grad_x / grad_y / grad_c
+ * all NULL (forward only) or all given, then g [cnt] and ws of 8 * ((cnt + 127) / 128 + 1) bytes are required.
+ * MM_ERR_ARG for null pointers, bad row ranges, m < 1, an unknown dtype, c_mode or op, c_min < 0 — before anything
+ * touches the GPU; MM_ERR_UNSUPPORTED for m > 16 and n > 32768 (pair offsets stay below 2^31 elements up to there).
+ * Nothing is allocated and nothing synchronises: every call can be captured in a HIP graph. */
+enum { MM_STEREO_C_FREE = 0, MM_STEREO_C_POSITIVE = 1, MM_STEREO_C_NEGATIVE = 2 };
+size_t mm_stereo_pdist_ws_bytes(int dtype, int64_t n, int m);
+int mm_stereo_pdist_fwd(int dtype, const void* x, int64_t n, int m, int64_t row_begin, int64_t row_end, int squared,
+                        const void* c_raw, int c_mode, double c_min, void* out, mm_stream_t stream);
+int mm_stereo_pdist_bwd(int dtype, const void* x, const void* g, int64_t n, int m, int64_t row_begin, int64_t row_end,
+                        int squared, const void* c_raw, int c_mode, double c_min, void* grad_x, void* grad_c, void* ws,
+                        mm_stream_t stream);
+int mm_stereo_dist(int dtype, const void* x, const void* y, const void* g, int64_t cnt, int m, int squared,
+                   const void* c_raw, int c_mode, double c_min, void* out, void* grad_x, void* grad_y, void* grad_c,
+                   void* ws, mm_stream_t stream);
+/* Per-point maps; x, u, y, out are [cnt, m]. */
+enum {
+  MM_STEREO_EGRAD2RGRAD = 0,   /* u / lambda_x^2                         impl/math.py:1452-1453              */
+  MM_STEREO_PROJU = 1,         /* u                                      universal.py:54-55                  */
+  MM_STEREO_EXP = 2,           /* project(exp_x(u))                      universal.py:66-71, math.py:720-727 */
+  MM_STEREO_EXP_NOPROJECT = 3, /* exp_x(u)                               (project=False)                     */
+  MM_STEREO_RETR = 4,          /* project(x + u)                         universal.py:73-74                  */
+  MM_STEREO_PROJX = 5,         /* c > 0 only, BALL_EPS 4e-3 / 1e-5       impl/math.py:142-156 (u unused)     */
+  MM_STEREO_LOG = 6,           /* log_x(y)                               impl/math.py:835-841 (u unused)     */
+  MM_STEREO_TRANSP = 7         /* u from x to y, gyration form           impl/math.py:1282-1298, 1359-1362   */
+};
+int mm_stereo_map(int dtype, int op, const void* x, const void* u, const void* y, int64_t cnt, int m, const void* c_raw,
+                  int c_mode, double c_min, void* out, mm_stream_t stream);
+/* Fused momentum-free RiemannianSGD update (rsgd.py:63-68, 82): r = egrad / lambda_x^2; r *= min(max_grad_norm / ||r||, 1)
+ * (skipped if max_grad_norm <= 0) with the norm the reference's class computes — Universal.norm calls math.norm without c,
+ * so ITS conformal factor is taken at c = 1 (universal.py:48-52) —; x_new = exact ? project(exp_x(-lr r)) :
+ * project(x - lr r).  x_new may equal x. */
+int mm_stereo_rsgd_step(int dtype, const void* x, const void* egrad, int64_t cnt, int m, const void* c_raw, int c_mode,
+                        double c_min, double lr, double max_grad_norm, int exact, void* x_new, mm_stream_t stream);
+/* products/embedding.py:37-46 in one launch: x / max(|x| / r_max, 1), then projx.  x_new may equal x. */
+int mm_stereo_stabilize(int dtype, const void* x, int64_t cnt, int m, const void* c_raw, int c_mode, double c_min,
+                        double r_max, void* x_new, mm_stream_t stream);
+
 /* ---- product embeddings ---------------------------------------------------- */
 /* Objective of a product embedding in one pass over the pair vectors (the element-wise part of
  * train.py:213-217 for several factors): with d2[k] the squared pair distances of factor k,

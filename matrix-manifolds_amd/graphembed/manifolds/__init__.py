@@ -4,6 +4,7 @@
   Lorentz, Sphere            inner-product manifolds        csrc/vec.hip, csrc/vec_gram.hip (matrix cores)
   Euclidean                  flat space                     csrc/vec.hip
   Grassmann, Stiefel         orthonormal frames             csrc/mat.hip
+  Stereographic              constant curvature, learnable  csrc/stereo.hip
 """
 from graphembed.manifolds.base import Manifold
 from graphembed.manifolds.spd import SymmetricPositiveDefinite
@@ -11,5 +12,6 @@ from graphembed.manifolds.lorentz import Lorentz
 from graphembed.manifolds.sphere import Sphere
 from graphembed.manifolds.euclidean import Euclidean
 from graphembed.manifolds.grassmann import Grassmann, Stiefel
+from graphembed.manifolds.stereographic import Stereographic
 
-__all__ = ['Manifold', 'SymmetricPositiveDefinite', 'Lorentz', 'Sphere', 'Euclidean', 'Grassmann', 'Stiefel']
+__all__ = ['Manifold', 'SymmetricPositiveDefinite', 'Lorentz', 'Sphere', 'Euclidean', 'Grassmann', 'Stiefel', 'Stereographic']

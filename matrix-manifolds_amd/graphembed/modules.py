@@ -512,3 +512,60 @@ class BatchedObjective(torch.nn.Module):
             if loss is not None:
                 return loss
         return self.objective_fn(gdists, self.embedding.compute_dists(indices, validated=True), *args, **kwargs)
+
+
+class StereographicProductEmbedding(torch.nn.Module):
+    """n points on a product of constant-curvature factors with learnable curvatures — the counterpart of the reference's
+    products/embedding.py:8-60 on `graphembed.manifolds.Stereographic`: `ds` lists the factors' dimensions, `kwargs` go to
+    every factor (c_init, c_min, keep_sign_fixed).  The squared distances of the factors are summed WITHOUT scales, as in
+    the reference; the curvature parameters are plain Euclidean parameters (the reference's grid gives them to Adam / SGD)."""
+
+    def __init__(self, n, ds, r_max=5.0, **kwargs):
+        super().__init__()
+        from graphembed.manifolds.stereographic import Stereographic
+        self.n = n
+        self.ds = list(ds)
+        self.r_max = r_max
+        self.n_components = len(self.ds)
+        self.manifolds = torch.nn.ModuleList([Stereographic(d, **kwargs) for d in self.ds])
+        # relies on default placement, as the reference does: move with `.to(device)`
+        self.xs = torch.nn.ParameterList([ManifoldParameter(data=man.rand(n), manifold=man) for man in self.manifolds])
+
+    def _apply(self, fn, *a, **k):
+        # Module.to()/cuda() rebuild Parameters; keep the manifold tag on them
+        mans = [p.manifold for p in self.xs]
+        out = super()._apply(fn, *a, **k)
+        for p, m in zip(self.xs, mans):
+            p.manifold = m
+        return out
+
+    @property
+    def device(self):
+        return self.xs[0].device
+
+    @property
+    def curvature_params(self):
+        for man in self.manifolds:
+            yield man.c
+
+    def burnin(self, value=True):
+        for p in self.curvature_params:
+            p.requires_grad_(not value)
+
+    @torch.no_grad()
+    def stabilize(self):
+        """The norm constraint and the projection of products/embedding.py:37-46, one launch per factor."""
+        for x, man in zip(self.xs, self.manifolds):
+            man.stabilize_(x, self.r_max)
+
+    def compute_dists(self, indices=None, validated=False):
+        if indices is not None and not validated:
+            indices = normalise_indices(indices, self.n)
+        return sum(man.pdist(take_rows(x, indices, validated=True), squared=True) for man, x in zip(self.manifolds, self.xs))
+
+    def fused_objective(self, objective_fn, gdists, i=None, **kwargs):
+        """No fused multi-factor objective kernel yet: BatchedObjective takes `objective_fn(gdists, compute_dists(i))`."""
+        return None
+
+    def __len__(self):
+        return self.n

@@ -101,6 +101,55 @@ def step_case(mans, n, dtype, fused=False, graph=False, pair_kernel=True, adam=F
     return {'n': n, 'pairs': P, 'dtype': str(dtype).split('.')[-1], 'step_us': t, 'pairs_per_s': P / (t * 1e-6)}
 
 
+def stereo_pdist_case(m, n, dtype):
+    """one constant-curvature factor (graphembed.manifolds.Stereographic): pdist forward | forward + backward (points and curvature)"""
+    man = M.Stereographic(m).to(device='cuda', dtype=dtype)
+    torch.manual_seed(42)
+    x = man.rand(n, out=torch.empty(0, dtype=dtype, device='cuda')).requires_grad_()
+    P = n * (n - 1) // 2
+    g = torch.randn(P, dtype=dtype, device='cuda')
+    fwd = timeit(lambda: man.pdist(x, squared=True))
+
+    def both():
+        d2 = man.pdist(x, squared=True)
+        torch.autograd.grad(d2, (x, man.c), g)
+    tot = timeit(both)
+    return {'n': n, 'pairs': P, 'dtype': str(dtype).split('.')[-1], 'fwd_us': fwd, 'fwd_bwd_us': tot, 'pairs_per_s': P / (tot * 1e-6)}
+
+
+def stereo_step_case(ds, n, dtype, graph=False):
+    """training step of a product of constant-curvature factors (StereographicProductEmbedding): compute_dists + stress loss +
+    backward + fused RSGD step of the points + SGD step of the curvatures + stabilize"""
+    from graphembed.modules import StereographicProductEmbedding
+    torch.manual_seed(0)
+    emb = StereographicProductEmbedding(n, ds).to(device='cuda', dtype=dtype)
+    P = n * (n - 1) // 2
+    target = torch.rand(P, dtype=dtype, device='cuda') * 0.99 + 0.01
+    fn = StressLoss()
+    opt = RiemannianSGD([dict(params=list(emb.xs), lr=1e-3, exact=True, max_grad_norm=20),
+                         dict(params=list(emb.curvature_params), lr=1e-4, exact=False, max_grad_norm=None)], lr=1e-3)
+
+    def step():
+        opt.zero_grad(set_to_none=True)
+        loss = fn(target, emb.compute_dists(None))
+        loss.backward(unit_seed(loss))
+        opt.step()
+        emb.stabilize()
+    if graph:
+        side = torch.cuda.Stream()
+        with torch.cuda.stream(side):
+            for _ in range(3):
+                step()
+        torch.cuda.current_stream().wait_stream(side)
+        gr = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(gr):
+            step()
+        t = timeit(gr.replay)
+    else:
+        t = timeit(step)
+    return {'n': n, 'pairs': P, 'dtype': str(dtype).split('.')[-1], 'step_us': t, 'pairs_per_s': P / (t * 1e-6)}
+
+
 CASES = {
     'c1_tree40_euclidean10_f64': lambda: pdist_case(M.Euclidean(10), 40, torch.float64),
     'c2_facebook_lorentz11_f32_gram': lambda: pdist_case(M.Lorentz(11), 4039, torch.float32),
@@ -181,6 +230,19 @@ CASES = {
     'c3_spd3_sne_excl_step_n5000_f32': lambda: step_case([M.SymmetricPositiveDefinite(3)], 5000, torch.float32, sne='excl'),
     'c3_spd3_sne_excl_step_n5000_f32_torchops': lambda: step_case([M.SymmetricPositiveDefinite(3)], 5000, torch.float32, sne='excl', native=False),
     'c3_spd3_sne_excl_step_n5000_f32_graph': lambda: step_case([M.SymmetricPositiveDefinite(3)], 5000, torch.float32, sne='excl', graph=True),
+    # constant curvature with learnable curvature (csrc/stereo.hip); the Lorentz rows of the same n, m and dtype are the yardstick
+    'stereo10_n4039_f32': lambda: stereo_pdist_case(10, 4039, torch.float32),
+    'stereo10_n4039_f64': lambda: stereo_pdist_case(10, 4039, torch.float64),
+    'lorentz10_n4039_f32_valu': lambda: pdist_case(_valu(M.Lorentz(10)), 4039, torch.float32),
+    'lorentz10_n4039_f64_valu': lambda: pdist_case(_valu(M.Lorentz(10)), 4039, torch.float64),
+    'stereo10_step_n4039_f32': lambda: stereo_step_case([10], 4039, torch.float32),
+    'stereo10_step_n4039_f32_graph': lambda: stereo_step_case([10], 4039, torch.float32, graph=True),
+    'lorentz10_step_n4039_f32': lambda: step_case([M.Lorentz(10)], 4039, torch.float32),
+    'stereo5_n1025_f32': lambda: stereo_pdist_case(5, 1025, torch.float32),
+    'lorentz5_n1025_f32_valu': lambda: pdist_case(_valu(M.Lorentz(5)), 1025, torch.float32),
+    'stereo5x5_step_n1025_f32': lambda: stereo_step_case([5, 5], 1025, torch.float32),
+    'stereo5x5_step_n1025_f32_graph': lambda: stereo_step_case([5, 5], 1025, torch.float32, graph=True),
+    'lorentz5x5_step_n1025_f32': lambda: step_case([M.Lorentz(5), M.Lorentz(5)], 1025, torch.float32),
     'c4_csphd_sne_incl_step_f32_graph': lambda: step_case([M.Lorentz(6), M.Sphere(6), M.SymmetricPositiveDefinite(2)], 1025, torch.float32, sne='incl', graph=True),
 }
 
