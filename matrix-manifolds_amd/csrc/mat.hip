@@ -5,7 +5,7 @@
 // stiefel.py:40-69, where every QR / SVD is shipped to the CPU (linalg/torch_batch.py:94-121).
 // Here:  Q of QR    = Householder with LAPACK's sign convention (so Q matches torch.qr),
 //        polar U V^T = Y (Y^T Y)^-1/2           via a p x p Jacobi eigensolve,
-//        U f(S) V^T of a thin SVD = Y V f(s)/s V^T  with (s^2, V) = eig(Y^T Y),
+//        U f(S) V^T of a thin SVD = Y V f(s)/s V^T  with (s^2, V) = eig(Y^T Y)  (exp; log: one-sided Jacobi on B itself),
 //        singular values of x^T y             = sqrt eig((x^T y)^T (x^T y)).
 // Points are stored [cnt][N][p] row-major; N is padded to NP in {4,6,9} (zero rows change
 // nothing), p in {1,2,3,4} is a template parameter.  The device functions live in mat_common.hpp
@@ -65,16 +65,27 @@ __global__ void mat_map_kernel(int kind, int op, const T* __restrict__ x, const 
         for (int k = 0; k < P; ++k) acc = Nm::fma(a[r][k], inv[c][k], acc);
         b[r][c] = acc;
       }
-    T s[P][P], w[P], v[P][P], f[P], m[P][P];
-    gram<T, NP, P>(b, b, s);
-    symeig<T, P>(s, w, v);
+    // U atan(S) V^T of B = U S V^T = (B V) diag(atan(s) / s) V^T with the singular values from a one-sided Jacobi on B itself
+    // (not from the eigenvalues of B^T B: see svd_onesided_tall)
+    T v[P][P], f[P];
+    svd_onesided_tall<T, NP, P>(b, v, T(16) * Nm::eps() * Nm::eps());
 #pragma unroll
     for (int k = 0; k < P; ++k) {
-      const T sg = Nm::sqrt(Nm::max(w[k], T(0)));
+      T nn = T(0);
+#pragma unroll
+      for (int r = 0; r < NP; ++r) nn = Nm::fma(b[r][k], b[r][k], nn);
+      const T sg = Nm::sqrt(nn);
       f[k] = (sg > T(1e-6)) ? atan_<T>(sg) / sg : T(1) - sg * sg * T(1.0 / 3.0);
     }
-    vfvt<T, P>(v, f, m);
-    mulr<T, NP, P>(b, m, o);
+#pragma unroll
+    for (int r = 0; r < NP; ++r)
+#pragma unroll
+      for (int c = 0; c < P; ++c) {
+        T acc = T(0);
+#pragma unroll
+        for (int k = 0; k < P; ++k) acc = Nm::fma(b[r][k] * f[k], v[c][k], acc);
+        o[r][c] = acc;
+      }
   }
   if (in) store<T, NP, P>(out + p * N * P, N, o);
 }

@@ -187,6 +187,59 @@ template <typename T, int P> __device__ __forceinline__ void inv_pp(const T (&m)
     for (int c = 0; c < P; ++c) inv[r][c] = a[r][P + c];
 }
 
+// One-sided Jacobi (Hestenes) on the columns of an NP x P matrix, in place: on exit b = B V has mutually orthogonal columns,
+// i.e. B = U diag(sigma) V^T with sigma_k = ||b_k|| and u_k = b_k / sigma_k (svd_onesided of smallmat.hpp with NP rows; the
+// same rotation, the same wave-uniform sweep loop).  log_x(y) needs it: B = (y - x x^T y)(x^T y)^-1 holds the tangents of the
+// principal angles, 1e3 - 1e4 next to O(1) for nearly orthogonal subspaces, and through the eigenvalues of B^T B everything
+// below sqrt(eps) sigma_max is rounding noise (0.2 absolute in fp32, 1e-9 in fp64 at Gr(8,4); the reference's own fp32: 5e-4).
+template <typename T, int NP, int P> __device__ __forceinline__ void svd_onesided_tall(T (&b)[NP][P], T (&v)[P][P], T tol2) {
+  using N = Num<T>;
+#pragma unroll
+  for (int r = 0; r < P; ++r)
+#pragma unroll
+    for (int c = 0; c < P; ++c) v[r][c] = (r == c) ? T(1) : T(0);
+  if constexpr (P == 1) return;
+  for (int sweep = 0; sweep < N::kMaxSweeps + 4; ++sweep) {
+    bool active = false;
+#pragma unroll
+    for (int p = 0; p < P - 1; ++p) {
+#pragma unroll
+      for (int q = p + 1; q < P; ++q) {
+        T app = T(0), aqq = T(0), apq = T(0);
+#pragma unroll
+        for (int r = 0; r < NP; ++r) {
+          app = N::fma(b[r][p], b[r][p], app);
+          aqq = N::fma(b[r][q], b[r][q], aqq);
+          apq = N::fma(b[r][p], b[r][q], apq);
+        }
+        active = active || (apq * apq > tol2 * (app * aqq));
+        const T h = aqq - app;
+        const T ah = N::abs(h) + T(1e-15);
+        const T sa_ = (h < T(0)) ? -apq : apq;
+        const T sa2 = sa_ + sa_;
+        const T rr = N::rsqrt(N::fma(ah, ah, sa2 * sa2));
+        const T x = N::fma(ah * rr, T(0.5), T(0.5));  // cos^2 t
+        const T ci = N::rsqrt(x);
+        const T c = x * ci;
+        const T sn = (sa_ * rr) * ci;
+#pragma unroll
+        for (int r = 0; r < NP; ++r) {
+          const T bp = b[r][p], bq = b[r][q];
+          b[r][p] = N::fma(c, bp, -sn * bq);
+          b[r][q] = N::fma(sn, bp, c * bq);
+        }
+#pragma unroll
+        for (int r = 0; r < P; ++r) {
+          const T vp = v[r][p], vq = v[r][q];
+          v[r][p] = N::fma(c, vp, -sn * vq);
+          v[r][q] = N::fma(sn, vp, c * vq);
+        }
+      }
+    }
+    if (!__any(active)) break;
+  }
+}
+
 template <typename T> __device__ __forceinline__ T acos_(T c);
 template <> __device__ __forceinline__ float acos_<float>(float c) { return ::acosf(c); }
 template <> __device__ __forceinline__ double acos_<double>(double c) { return ::acos(c); }
@@ -216,9 +269,14 @@ __device__ __forceinline__ T grass_pair(const T (&g)[P][P], T (&dg)[P][P]) {
     const T a = g[0][0], b = g[0][1], c = g[1][0], d = g[1][1];
     const T S1 = a * a + b * b + c * c + d * d;
     const T Dd = a * a + b * b - c * c - d * d, E = a * c + b * d;
-    const T R = N::sqrt(N::max(N::fma(Dd, Dd, T(4) * E * E), T(kEps)));
+    const T R2 = N::fma(Dd, Dd, T(4) * E * E);
+    const T R = N::sqrt(N::max(R2, T(kEps)));
     const T s1 = N::sqrt(N::max(T(0.5) * (S1 + R), T(kEps)));
-    const T s2 = N::sqrt(N::max(T(0.5) * (S1 - R), T(kEps)));
+    // (S1 - R)/2 = (S1^2 - R^2) / (2 (S1 + R)) and S1^2 - R^2 = 4 det^2 while the clamp on S2 is idle: the same number without
+    // the cancellation, which costs eps S1 / sigma_2 of sigma_2 next to orthogonal subspaces (fp32, Gr(9,2): 2.4e-4 of d^2, 16 x
+    // the reference's own fp32); under the clamp the reference's biased value is kept as it is
+    const T det = N::fma(a, d, -b * c);
+    const T s2 = N::sqrt(N::max(R2 >= T(kEps) ? (T(2) * det * det) / (S1 + R) : T(0.5) * (S1 - R), T(kEps)));
     const T c1 = N::min(s1, T(1 - 1e-16)), c2 = N::min(s2, T(1 - 1e-16));
     const T t1 = acos_<T>(c1), t2 = acos_<T>(c2);
     if (WANT_GRAD) {

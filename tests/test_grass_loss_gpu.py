@@ -1,6 +1,8 @@
 """The fused Grassmann objective (mm_grass_pdist_loss through Grassmann.pdist_loss / ManifoldEmbedding.fused_objective)
 against the fp64 oracle of oracle/ref_port.py, with the measured tolerance rule of tests/grass_cases.py: the route the
-package took before (compute_dists -> objective -> autograd, on the GPU, same inputs) is the yardstick."""
+package took before (compute_dists -> objective -> autograd, on the GPU, same inputs) is the yardstick.  That yardstick shares
+the device code under test; the absolute check of both routes is tests/test_mat_oracle_gpu.py (pdist forward / backward at all 26
+shapes of mat_cases.SHAPES, the fused objective at (2,1) (3,3) (4,4) (6,4) (7,3) (8,4) (9,1), fp32 and fp64)."""
 import os
 import sys
 

@@ -1,7 +1,9 @@
 """The fused RiemannianSGD kernels of Grassmann / Stiefel points (mm_mat_rsgd_step, mm_mat_rsgd_momentum_step through
 _MatrixManifold.rsgd_step / rsgd_momentum_step and RiemannianSGD) against oracle/ref_port.rsgd_step in fp64, with the
 measured tolerance rule of tests/grass_cases.py: the yardstick is the explicit egrad2rgrad / norm / clip / retr|exp /
-transp sequence of per-operation launches on the GPU, same inputs."""
+transp sequence of per-operation launches on the GPU, same inputs.  That yardstick shares the device code under test; the
+absolute check is tests/test_mat_oracle_gpu.py (every per-operation map at all 26 shapes of mat_cases.SHAPES, both kinds, and the
+fused step at (2,1) (3,3) (4,4) (6,4) (7,3) (8,4) (9,1), fp32 and fp64, under the rule of tests/mat_cases.py)."""
 import os
 import sys
 
