@@ -481,6 +481,41 @@ int mm_stereo_rsgd_step(int dtype, const void* x, const void* egrad, int64_t cnt
 /* products/embedding.py:37-46 in one launch: x / max(|x| / r_max, 1), then projx.  x_new may equal x. */
 int mm_stereo_stabilize(int dtype, const void* x, int64_t cnt, int m, const void* c_raw, int c_mode, double c_min,
                         double r_max, void* x_new, mm_stream_t stream);
+/* Products of nf constant-curvature factors (products/embedding.py:8-60 of the reference): m = sum_k max(d_k^2, 1e-8), the
+ * factors' squared distances summed in factor order WITHOUT scales, every factor with its own (c_raw, c_mode, c_min).  The
+ * factor list `f` is HOST memory, read at call time and passed to the kernels by value; x, c_raw, grad_x, grad_c are
+ * device memory.
+ * mm_stereo_product_pdist_fwd: the summed pair vector of the rows [row_begin, row_end) in ONE launch (grad_x / grad_c of
+ * the factors are not touched and may be NULL).
+ * mm_stereo_product_loss: one pass over every unordered pair and all factors that evaluates the objective on m and writes
+ * grad_x [n, m_k] and grad_c [1] of EVERY factor (both OVERWRITTEN with this shard's partial gradients, with respect to
+ * c_raw) and loss_out [1].  loss_kind MM_LOSS_STRESS / MM_LOSS_QUOTIENT: target, alpha, eps, terms and loss_params
+ * {alpha, eps} (device, may be NULL) as for mm_grass_pdist_loss, without a scale.  MM_LOSS_NONE: `target` is the upstream
+ * gradient d L / d m per pair (the backward of the forward above), nothing is written to loss_out (may be NULL).
+ * Three launches whatever nf is: the pair kernel, one finalize over (node, factor), one fixed-order fp64 reduction of the
+ * loss and curvature partials.  No float atomics: results are bitwise reproducible; shards of the row range sum to the whole.
+ * An empty row range, a range without pairs or n < 2 writes zero gradients, zero grad_c and a zero loss.
+ * ws: mm_stereo_product_ws_bytes(dtype, n, nf, m) bytes (0 for arguments the library refuses): the factors' slabs, each as
+ * mm_stereo_pdist_ws_bytes describes, plus (nf + 1) fp64 partials per tile; it needs no clearing.
+ * 1 <= nf <= 8 (more: MM_ERR_UNSUPPORTED), 1 <= m <= 16 and n <= 32768 as above; MM_ERR_ARG (null pointers, bad row ranges,
+ * nf < 1, m < 1, an unknown dtype, loss_kind or c_mode, c_min < 0) is reported first, both before anything touches the
+ * GPU.  Nothing is allocated and nothing synchronises: every call can be captured in a HIP graph, and a captured step
+ * follows the optimizer's updates of every c_raw. */
+typedef struct mm_stereo_factor {
+  const void* x;     /* [n, m] */
+  const void* c_raw; /* one element of `dtype`, device memory */
+  void* grad_x;      /* [n, m], OVERWRITTEN (may be NULL for the forward) */
+  void* grad_c;      /* [1],    OVERWRITTEN (may be NULL for the forward) */
+  double c_min;
+  int32_t m, c_mode;
+} mm_stereo_factor;
+size_t mm_stereo_product_ws_bytes(int dtype, int64_t n, int nf, const int32_t* m);
+int mm_stereo_product_pdist_fwd(int dtype, const mm_stereo_factor* f, int nf, int64_t n, int64_t row_begin,
+                                int64_t row_end, void* out, mm_stream_t stream);
+int mm_stereo_product_loss(int dtype, int loss_kind, const mm_stereo_factor* f, int nf, const void* target, int64_t n,
+                           int64_t row_begin, int64_t row_end, double alpha, double eps, int terms,
+                           const double* loss_params, void* loss_out /* [1]; may be NULL for MM_LOSS_NONE */, void* ws,
+                           mm_stream_t stream);
 
 /* ---- product embeddings ---------------------------------------------------- */
 /* Objective of a product embedding in one pass over the pair vectors (the element-wise part of

@@ -29,6 +29,7 @@
 #include <type_traits>
 
 #include "../../include/mm_manifolds.h"
+#include "loss.hpp"
 
 namespace mm {
 namespace stereo {
@@ -642,6 +643,441 @@ int bwd(const T* x, const T* g, int64_t n, int m, int64_t rb, int64_t re, int sq
   return status();
 }
 
+
+// ---- products of constant-curvature factors -------------------------------------------------------------------------------
+// m = sum_k max(d_k^2, 1e-8) over up to kMaxFactors factors (products/embedding.py:48-52 of the reference: no scales), every
+// factor with a curvature of its own.  The forward writes the summed pair vector in one launch; the objective kernel visits every
+// unordered pair once and ALL factors: (a) m, the loss term and g = d loss / d m per pair (g is read from `target`'s place with
+// MM_LOSS_NONE), (b) factor by factor the phases of pdist_bwd_kernel with that g - the tiles sA / sAt are reused, g stays in RW
+// registers of the lane that owns the column (the phase-1 mapping is the same for every factor), the records go to the factor's
+// segment of the slab.  The transcendental part of a factor is evaluated TWICE (pair_value in (a), pair_grad in (b)): carrying
+// {t, phi} of every factor from (a) to (b) would cost 2 K RW registers per lane, g costs RW.  The loss and the curvature sums leave
+// as (1 + nf) fp64 partials per workgroup and are added in fixed order by product_reduce_kernel.
+constexpr int kMaxFactors = 8;
+template <typename T> struct PFactor {
+  const T* x;
+  const T* c_raw;
+  T* grad_x;
+  T* grad_c;
+  T* slab;        // this factor's records
+  double c_min;
+  int m, c_mode;
+};
+template <typename T> struct PFactors {
+  PFactor<T> f[kMaxFactors];
+  int nf;
+};
+
+template <typename T, int MP>
+__global__ __launch_bounds__(kC* kWaves) void product_fwd_kernel(PFactors<T> pf, int n, int rb, int re, T* __restrict__ out) {
+  constexpr int RW = kC / kWaves;
+  const int bj = blockIdx.x, bi = rb / kC + blockIdx.y;
+  if (bj < bi) return;
+  __shared__ T sx[kC][MP + 1];
+  __shared__ T ss[kC];
+  __shared__ T sacc[kC * kC];       // the tile's sums: a cell is written and read by one lane only
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int j = bj * kC + lane, jc = min(j, n - 1);
+  for (int f = 0; f < pf.nf; ++f) {
+    const T* __restrict__ x = pf.f[f].x;
+    const int m = pf.f[f].m;
+    const T c = load_curv(pf.f[f].c_raw, pf.f[f].c_mode, pf.f[f].c_min).c;
+    if (f) __syncthreads();         // the previous factor's rows have been read
+    if (threadIdx.x < kC) {
+      const int i = min(bi * kC + int(threadIdx.x), n - 1);
+      T a = 0;
+#pragma unroll
+      for (int k = 0; k < MP; ++k) {
+        const T v = k < m ? x[size_t(i) * m + k] : T(0);
+        sx[threadIdx.x][k] = v;
+        a += v * v;
+      }
+      ss[threadIdx.x] = 1 - c * a;
+    }
+    T xj[MP], b = 0;
+#pragma unroll
+    for (int k = 0; k < MP; ++k) {
+      xj[k] = k < m ? x[size_t(jc) * m + k] : T(0);
+      b += xj[k] * xj[k];
+    }
+    const T sj = 1 - c * b;
+    __syncthreads();
+#pragma unroll 4
+    for (int r = 0; r < RW; ++r) {
+      const int il = wave * RW + r, i = bi * kC + il;
+      if (i < rb || i >= re) continue;   // (wave-uniform)
+      T q = 0;
+#pragma unroll
+      for (int k = 0; k < MP; ++k) {
+        const T d = sx[il][k] - xj[k];
+        q += d * d;
+      }
+      const T v = pair_value<T>(q, ss[il] * sj + c * q, c, true);
+      sacc[il * kC + lane] = f ? sacc[il * kC + lane] + v : v;   // summed in factor order
+    }
+  }
+  const int64_t base = poff(n, rb);
+  const bool interior = bj > bi && bj * kC + kC <= n;
+  for (int r = 0; r < RW; ++r) {
+    const int il = wave * RW + r, i = bi * kC + il;
+    if (i < rb || i >= re) continue;
+    if (interior || (j > i && j < n)) out[poff(n, i) - base + (j - i - 1)] = sacc[il * kC + lane];
+  }
+}
+
+template <typename T, int MP, int LOSS>
+__global__ __launch_bounds__(kC* kWaves) void product_loss_kernel(PFactors<T> pf, const T* __restrict__ target, int n, int rb, int re,
+                                                                  int bi0, int nbr, LossArgs<T> la, double* __restrict__ partials) {
+  constexpr int TR = Tile<T>::rows, RW = TR / kWaves, CW = kC / kWaves, LD = kC + 1, UNR = sizeof(T) == 4 ? 2 : 1, KUN = sizeof(T) == 4 ? MP : 4;
+  const int bj = blockIdx.x, bi = bi0 + blockIdx.y;
+  const int slot_p = blockIdx.y * gridDim.x + blockIdx.x, tiles = gridDim.x * gridDim.y;
+  const int nf = pf.nf;
+  if (bj < (bi * TR + 1) / kC) return;   // no pair i < j in this tile: it leaves no partials, product_reduce_kernel skips its slots
+  __shared__ T sxr[TR][MP + 1], sxc[kC][MP + 1];
+  __shared__ T sar[TR], sbc[kC];
+  __shared__ T sA[TR * LD], sAt[TR * LD];
+  __shared__ T redc[MP + 1][kC], redr[MP + 1][TR];
+  __shared__ double scv[kWaves];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int j = bj * kC + lane;
+  double* const ptile = partials + slot_p;
+  const int pstride = tiles;
+
+  // a factor's points of the tile: rows, columns and their squared norms
+  auto load_points = [&](const T* __restrict__ x, int m) {
+    if (tid < TR) {
+      const int i = min(bi * TR + tid, n - 1);
+      T a = 0;
+#pragma unroll
+      for (int k = 0; k < MP; ++k) {
+        const T v = k < m ? x[size_t(i) * m + k] : T(0);
+        sxr[tid][k] = v;
+        a += v * v;
+      }
+      sar[tid] = a;
+    }
+    if (wave == 1) {
+      const int jc = min(j, n - 1);
+      T b = 0;
+#pragma unroll
+      for (int k = 0; k < MP; ++k) {
+        const T v = k < m ? x[size_t(jc) * m + k] : T(0);
+        sxc[lane][k] = v;
+        b += v * v;
+      }
+      sbc[lane] = b;
+    }
+  };
+  // the fp64 sum of one value per thread, in fixed order, into this tile's partial `which`
+  auto tile_sum = [&](T v, int which) {
+    double d = double(v);
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) d += __shfl_xor(d, s, 64);
+    if (lane == 0) scv[wave] = d;
+    __syncthreads();
+    if (tid == 0) ptile[size_t(which) * pstride] = ((scv[0] + scv[1]) + scv[2]) + scv[3];
+    __syncthreads();
+  };
+
+  // (a) g of the lane's RW pairs: d loss / d m at m = sum_k d_k^2, or the upstream value
+  T gr[RW];
+#pragma unroll
+  for (int r = 0; r < RW; ++r) gr[r] = 0;
+  if constexpr (LOSS != MM_LOSS_NONE) {
+    for (int f = 0; f < nf; ++f) {
+      const T c = load_curv(pf.f[f].c_raw, pf.f[f].c_mode, pf.f[f].c_min).c;
+      if (f) __syncthreads();
+      load_points(pf.f[f].x, pf.f[f].m);
+      __syncthreads();
+      const T sj = 1 - c * sbc[lane];
+#pragma unroll UNR
+      for (int r = 0; r < RW; ++r) {   // (r is wave-uniform: gr[r] is a register picked by a scalar index, not memory)
+        const int il = wave * RW + r;
+        T q = 0;
+#pragma unroll KUN
+        for (int k = 0; k < MP; ++k) {
+          const T d = sxr[il][k] - sxc[lane][k];
+          q += d * d;
+        }
+        gr[r] += pair_value<T>(q, (1 - c * sar[il]) * sj + c * q, c, true);   // summed in factor order, as the forward does
+      }
+    }
+    __syncthreads();
+  }
+  loss_resolve<T, LOSS>(la);
+  const int64_t base = poff(n, rb);
+  T lacc = 0;
+#pragma unroll
+  for (int r = 0; r < RW; ++r) {
+    const int i = bi * TR + wave * RW + r;
+    const bool live = j > i && j < n && i >= rb && i < re;
+    const T tg = live ? target[poff(n, i) - base + (j - i - 1)] : T(1);
+    if constexpr (LOSS == MM_LOSS_NONE) {
+      gr[r] = live ? tg : T(0);
+    } else {
+      T dldm;
+      const T l = loss_term<T, LOSS>(gr[r], tg, la, dldm);
+      lacc += live ? l : T(0);
+      gr[r] = live ? dldm : T(0);
+    }
+  }
+  if constexpr (LOSS != MM_LOSS_NONE) tile_sum(lacc, 0);
+  else if (tid == 0) ptile[0] = 0.0;
+
+  // (b) factor by factor: the phases of pdist_bwd_kernel with g from the registers
+  for (int f = 0; f < nf; ++f) {
+    const T c = load_curv(pf.f[f].c_raw, pf.f[f].c_mode, pf.f[f].c_min).c;
+    const int m = pf.f[f].m;
+    T* __restrict__ slab = pf.f[f].slab;
+    if (f || LOSS != MM_LOSS_NONE) __syncthreads();
+    load_points(pf.f[f].x, m);
+    __syncthreads();
+    T cacc = 0;
+    {
+      const T b = sbc[lane], sj = 1 - c * b;
+#pragma unroll UNR
+      for (int r = 0; r < RW; ++r) {
+        const int il = wave * RW + r;
+        T q = 0, p = 0;
+#pragma unroll KUN
+        for (int k = 0; k < MP; ++k) {
+          const T xi = sxr[il][k], xj = sxc[lane][k], d = xi - xj;
+          q += d * d;
+          p += xi * xj;
+        }
+        const T a = sar[il], gv = gr[r];
+        T A = 0, At = 0, dcp = 0;
+        if (gv != T(0)) pair_grad<T>(q, p, a, b, (1 - c * a) * sj + c * q, c, gv, true, A, At, dcp);   // (g = 0: no pair here, or none of its business)
+        sA[il * LD + lane] = A;
+        sAt[il * LD + lane] = At;
+        cacc += dcp;
+      }
+    }
+    __syncthreads();
+    // columns
+    T cw[MP], xo[MP], cvs = 0;
+#pragma unroll
+    for (int k = 0; k < MP; ++k) {
+      cw[k] = 0;
+      xo[k] = sxc[lane][k];
+    }
+#pragma unroll UNR
+    for (int r = 0; r < RW; ++r) {
+      const int il = wave * RW + r;
+      const T A = sA[il * LD + lane], At = sAt[il * LD + lane];
+      const T W = A - c * At;
+      cvs += c * At * (1 - c * sar[il]);
+#pragma unroll
+      for (int k = 0; k < MP; ++k) cw[k] += W * (xo[k] - sxr[il][k]);
+    }
+    for (int wv = 0; wv < kWaves; ++wv) {
+      if (wave == wv) {
+#pragma unroll
+        for (int k = 0; k < MP; ++k) redc[k][lane] = wv == 0 ? cw[k] : redc[k][lane] + cw[k];
+        redc[MP][lane] = wv == 0 ? cvs : redc[MP][lane] + cvs;
+      }
+      __syncthreads();
+    }
+    // rows: the tile turned
+    T rw[MP], rvs = 0;
+#pragma unroll
+    for (int k = 0; k < MP; ++k) rw[k] = 0;
+    if (lane < TR) {
+#pragma unroll
+      for (int k = 0; k < MP; ++k) xo[k] = sxr[lane][k];
+#pragma unroll UNR
+      for (int jj = 0; jj < CW; ++jj) {
+        const int jl = wave * CW + jj;
+        const T A = sA[lane * LD + jl], At = sAt[lane * LD + jl];
+        const T W = A - c * At;
+        rvs += c * At * (1 - c * sbc[jl]);
+#pragma unroll
+        for (int k = 0; k < MP; ++k) rw[k] += W * (xo[k] - sxc[jl][k]);
+      }
+    }
+    for (int wv = 0; wv < kWaves; ++wv) {
+      if (wave == wv && lane < TR) {
+#pragma unroll
+        for (int k = 0; k < MP; ++k) redr[k][lane] = wv == 0 ? rw[k] : redr[k][lane] + rw[k];
+        redr[MP][lane] = wv == 0 ? rvs : redr[MP][lane] + rvs;
+      }
+      __syncthreads();
+    }
+    const size_t ns = size_t(n), comps = size_t(m) + 1;
+    if (wave == 0 && j < n) {           // column records of row block bi
+      T* rec = slab + size_t(bi) * comps * ns + j;
+      for (int k = 0; k < m; ++k) rec[k * ns] = redc[k][lane];
+      rec[size_t(m) * ns] = redc[MP][lane];
+    }
+    if (wave == 1 && lane < TR && bi * TR + lane < n) {   // row records of column block bj
+      T* rec = slab + size_t(nbr + bj) * comps * ns + (bi * TR + lane);
+      for (int k = 0; k < m; ++k) rec[k * ns] = redr[k][lane];
+      rec[size_t(m) * ns] = redr[MP][lane];
+    }
+    tile_sum(cacc, 1 + f);
+  }
+}
+
+// grad_x of factor blockIdx.y: a node's records in slot order, as pdist_bwd_finalize_kernel adds them
+template <typename T>
+__global__ __launch_bounds__(256) void product_finalize_kernel(PFactors<T> pf, int n, int rb, int re, int nbr, int nbc) {
+  constexpr int TR = Tile<T>::rows;
+  const int v = blockIdx.x * 256 + threadIdx.x;
+  if (v >= n) return;
+  const PFactor<T>& F = pf.f[blockIdx.y];
+  const T* __restrict__ x = F.x;
+  const T* __restrict__ slab = F.slab;
+  T* __restrict__ grad = F.grad_x;
+  const int m = F.m;
+  const size_t ns = size_t(n), comps = size_t(m) + 1;
+  T acc[kMaxDim + 1];
+#pragma unroll
+  for (int k = 0; k <= kMaxDim; ++k) acc[k] = 0;
+  if (re > rb) {
+    const int bi0 = rb / TR, bi1 = (re - 1) / TR;
+    const int last = v >= 1 ? min(bi1, (v - 1) / TR) : -1;
+    for (int s = bi0; s <= last; ++s) {
+      const T* rec = slab + size_t(s) * comps * ns + v;
+#pragma unroll
+      for (int k = 0; k <= kMaxDim; ++k)
+        if (k <= m) acc[k] += rec[k * ns];
+    }
+    if (v >= rb && v < re) {
+      const int bv = v / TR;
+      for (int s = (bv * TR + 1) / kC; s < nbc; ++s) {
+        const T* rec = slab + size_t(nbr + s) * comps * ns + v;
+#pragma unroll
+        for (int k = 0; k <= kMaxDim; ++k)
+          if (k <= m) acc[k] += rec[k * ns];
+      }
+    }
+  }
+  T vs = 0;
+#pragma unroll
+  for (int k = 0; k <= kMaxDim; ++k)
+    if (k == m) vs = acc[k];
+#pragma unroll
+  for (int k = 0; k < kMaxDim; ++k)
+    if (k < m) grad[size_t(v) * m + k] = acc[k] + vs * x[size_t(v) * m + k];
+}
+
+// block 0: the loss; block 1 + k: grad_c of factor k = dc/dc_raw * its partials - fp64, fixed order
+template <typename T>
+__global__ __launch_bounds__(256) void product_reduce_kernel(PFactors<T> pf, const double* __restrict__ partials, int count, int gx,
+                                                             int bi0, T* __restrict__ loss_out) {
+  constexpr int TR = Tile<T>::rows;
+  __shared__ double sh[256];
+  const int which = blockIdx.x;
+  const double* __restrict__ p = partials + size_t(which) * count;
+  double s = 0;
+  for (int k = threadIdx.x; k < count; k += 256) {
+    const int by = k / gx, bx = k - by * gx;
+    if (bx >= ((bi0 + by) * TR + 1) / kC) s += p[k];   // (a tile without a pair i < j wrote nothing)
+  }
+  sh[threadIdx.x] = s;
+  __syncthreads();
+  for (int h = 128; h >= 1; h >>= 1) {
+    if (int(threadIdx.x) < h) sh[threadIdx.x] += sh[threadIdx.x + h];
+    __syncthreads();
+  }
+  if (threadIdx.x != 0) return;
+  if (which == 0) {
+    if (loss_out) loss_out[0] = T(sh[0]);
+  } else {
+    const PFactor<T>& F = pf.f[which - 1];
+    F.grad_c[0] = T(sh[0] * double(load_curv(F.c_raw, F.c_mode, F.c_min).dc));
+  }
+}
+
+inline size_t product_partial_bytes(size_t el, int64_t n, int nf) {
+  const size_t nbr = size_t((n + rows_of(el) - 1) / rows_of(el)), nbc = size_t((n + kC - 1) / kC);
+  return round256(sizeof(double) * (size_t(nf + 1) * nbr * nbc + 1));
+}
+// what the product calls refuse, in the order MM_ERR_ARG before MM_ERR_UNSUPPORTED
+inline int product_check(int dtype, const mm_stereo_factor* f, int nf, int64_t n, int64_t rb, int64_t re, bool back) {
+  if ((dtype != MM_F32 && dtype != MM_F64) || !f || nf < 1 || n < 0 || rb < 0 || re < rb || re > n) return MM_ERR_ARG;
+  bool wide = nf > kMaxFactors;
+  for (int k = 0; k < nf && k < 64; ++k) {
+    if (f[k].m < 1 || bad_curv(f[k].c_raw, f[k].c_mode, f[k].c_min)) return MM_ERR_ARG;
+    if (back && !f[k].grad_c) return MM_ERR_ARG;
+    if (n >= 1 && back && (!f[k].x || !f[k].grad_x)) return MM_ERR_ARG;
+    if (n >= 2 && !back && has_pairs(n, rb, re) && !f[k].x) return MM_ERR_ARG;
+    wide = wide || f[k].m > kMaxDim;
+  }
+  return wide || n > kMaxNodes ? MM_ERR_UNSUPPORTED : MM_OK;
+}
+template <typename T> PFactors<T> product_args(const mm_stereo_factor* f, int nf, int64_t n, void* ws, int* widest) {
+  PFactors<T> pf{};
+  pf.nf = nf;
+  char* at = static_cast<char*>(ws);
+  *widest = 1;
+  for (int k = 0; k < nf; ++k) {
+    pf.f[k] = PFactor<T>{static_cast<const T*>(f[k].x), static_cast<const T*>(f[k].c_raw), static_cast<T*>(f[k].grad_x),
+                         static_cast<T*>(f[k].grad_c), reinterpret_cast<T*>(at), f[k].c_min, f[k].m, f[k].c_mode};
+    if (ws) at += slab_bytes(sizeof(T), n, f[k].m);
+    *widest = f[k].m > *widest ? f[k].m : *widest;
+  }
+  return pf;
+}
+
+template <typename T>
+int product_fwd(const mm_stereo_factor* f, int nf, int64_t n, int64_t rb, int64_t re, T* out, hipStream_t st) {
+  int widest;
+  const PFactors<T> pf = product_args<T>(f, nf, n, nullptr, &widest);
+  const dim3 grid(unsigned((n + kC - 1) / kC), unsigned((re - 1) / kC - rb / kC + 1)), wg(kC * kWaves);
+  switch (pad_of(widest)) {
+    case 4: product_fwd_kernel<T, 4><<<grid, wg, 0, st>>>(pf, int(n), int(rb), int(re), out); break;
+    case 8: product_fwd_kernel<T, 8><<<grid, wg, 0, st>>>(pf, int(n), int(rb), int(re), out); break;
+    default: product_fwd_kernel<T, 16><<<grid, wg, 0, st>>>(pf, int(n), int(rb), int(re), out); break;
+  }
+  return status();
+}
+
+template <typename T, int LOSS>
+void product_loss_launch(int pad, dim3 grid, hipStream_t st, const PFactors<T>& pf, const T* target, int n, int rb, int re, int bi0,
+                         int nbr, LossArgs<T> la, double* partials) {
+  const dim3 wg(kC * kWaves);
+  switch (pad) {
+    case 4: product_loss_kernel<T, 4, LOSS><<<grid, wg, 0, st>>>(pf, target, n, rb, re, bi0, nbr, la, partials); break;
+    case 8: product_loss_kernel<T, 8, LOSS><<<grid, wg, 0, st>>>(pf, target, n, rb, re, bi0, nbr, la, partials); break;
+    default: product_loss_kernel<T, 16, LOSS><<<grid, wg, 0, st>>>(pf, target, n, rb, re, bi0, nbr, la, partials); break;
+  }
+}
+
+template <typename T>
+int product_loss(int loss_kind, const mm_stereo_factor* f, int nf, const T* target, int64_t n, int64_t rb, int64_t re, double alpha,
+                 double eps, int terms, const double* loss_params, T* loss_out, void* ws, hipStream_t st) {
+  constexpr int TR = Tile<T>::rows;
+  int widest;
+  const PFactors<T> pf = product_args<T>(f, nf, n, ws, &widest);
+  const int nbr = int((n + TR - 1) / TR), nbc = int((n + kC - 1) / kC);
+  size_t slabs = 0;
+  for (int k = 0; k < nf; ++k) slabs += slab_bytes(sizeof(T), n, f[k].m);
+  double* partials = reinterpret_cast<double*>(static_cast<char*>(ws) + slabs);
+  const bool pairs = n >= 2 && has_pairs(n, rb, re);
+  int count = 0, bi0 = 0;
+  if (pairs) {
+    bi0 = int(rb / TR);
+    const int bi1 = int((re - 1) / TR);
+    const dim3 grid(nbc, bi1 - bi0 + 1);
+    count = int(grid.x * grid.y);
+    LossArgs<T> la{nullptr, T(alpha), T(eps), terms, nullptr, loss_params};
+    const int pad = pad_of(widest);
+    if (loss_kind == MM_LOSS_STRESS)
+      product_loss_launch<T, MM_LOSS_STRESS>(pad, grid, st, pf, target, int(n), int(rb), int(re), bi0, nbr, la, partials);
+    else if (loss_kind == MM_LOSS_QUOTIENT)
+      product_loss_launch<T, MM_LOSS_QUOTIENT>(pad, grid, st, pf, target, int(n), int(rb), int(re), bi0, nbr, la, partials);
+    else
+      product_loss_launch<T, MM_LOSS_NONE>(pad, grid, st, pf, target, int(n), int(rb), int(re), bi0, nbr, la, partials);
+  }
+  if (n >= 1)   // (a range without pairs: the sums over no record are the zero gradients)
+    product_finalize_kernel<T><<<dim3(unsigned((n + 255) / 256), unsigned(nf)), dim3(256), 0, st>>>(pf, int(n), int(rb), pairs ? int(re) : int(rb), nbr, nbc);
+  product_reduce_kernel<T><<<dim3(unsigned(nf + 1)), dim3(256), 0, st>>>(pf, partials, count, nbc, bi0, loss_kind == MM_LOSS_NONE ? nullptr : loss_out);
+  return status();
+}
+
 }  // namespace stereo
 }  // namespace mm
 
@@ -777,6 +1213,47 @@ int mm_stereo_stabilize(int dtype, const void* x, int64_t cnt, int m, const void
     stabilize_kernel<T><<<grid, wg, 0, st>>>(static_cast<const T*>(x), cnt, m, static_cast<const T*>(c_raw), c_mode, c_min, T(r_max), static_cast<T*>(x_new));
   }
   return status();
+}
+
+size_t mm_stereo_product_ws_bytes(int dtype, int64_t n, int nf, const int32_t* m) {
+  if ((dtype != MM_F32 && dtype != MM_F64) || n < 0 || n > kMaxNodes || nf < 1 || nf > kMaxFactors || !m) return 0;
+  const size_t el = dtype == MM_F64 ? 8 : 4;
+  size_t b = product_partial_bytes(el, n, nf);
+  for (int k = 0; k < nf; ++k) {
+    if (m[k] < 1 || m[k] > kMaxDim) return 0;
+    b += slab_bytes(el, n, m[k]);
+  }
+  return b;
+}
+
+int mm_stereo_product_pdist_fwd(int dtype, const mm_stereo_factor* f, int nf, int64_t n, int64_t row_begin, int64_t row_end, void* out,
+                                mm_stream_t stream) {
+  const int rc = product_check(dtype, f, nf, n, row_begin, row_end, false);
+  if (rc == MM_ERR_ARG) return rc;
+  if (n >= 2 && n <= kMaxNodes && has_pairs(n, row_begin, row_end) && !out) return MM_ERR_ARG;
+  if (rc != MM_OK) return rc;
+  if (n < 2 || !has_pairs(n, row_begin, row_end)) return MM_OK;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (dtype == MM_F32) return product_fwd<float>(f, nf, n, row_begin, row_end, static_cast<float*>(out), st);
+  return product_fwd<double>(f, nf, n, row_begin, row_end, static_cast<double*>(out), st);
+}
+
+int mm_stereo_product_loss(int dtype, int loss_kind, const mm_stereo_factor* f, int nf, const void* target, int64_t n, int64_t row_begin,
+                           int64_t row_end, double alpha, double eps, int terms, const double* loss_params, void* loss_out, void* ws,
+                           mm_stream_t stream) {
+  const int rc = product_check(dtype, f, nf, n, row_begin, row_end, true);
+  if (rc == MM_ERR_ARG) return rc;
+  if ((loss_kind != MM_LOSS_NONE && loss_kind != MM_LOSS_STRESS && loss_kind != MM_LOSS_QUOTIENT) || !ws ||
+      (loss_kind != MM_LOSS_NONE && !loss_out))
+    return MM_ERR_ARG;
+  if (n >= 2 && n <= kMaxNodes && has_pairs(n, row_begin, row_end) && !target) return MM_ERR_ARG;
+  if (rc != MM_OK) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (dtype == MM_F32)
+    return product_loss<float>(loss_kind, f, nf, static_cast<const float*>(target), n, row_begin, row_end, alpha, eps, terms, loss_params,
+                               static_cast<float*>(loss_out), ws, st);
+  return product_loss<double>(loss_kind, f, nf, static_cast<const double*>(target), n, row_begin, row_end, alpha, eps, terms, loss_params,
+                              static_cast<double*>(loss_out), ws, st);
 }
 
 }  // extern "C"

@@ -128,6 +128,9 @@ SIGNATURES = {
     'mm_stereo_map': (_i, [_i, _i, _vp, _vp, _vp, _i64, _i, _vp, _i, _dbl, _vp, _vp]),
     'mm_stereo_rsgd_step': (_i, [_i, _vp, _vp, _i64, _i, _vp, _i, _dbl, _dbl, _dbl, _i, _vp, _vp]),
     'mm_stereo_stabilize': (_i, [_i, _vp, _i64, _i, _vp, _i, _dbl, _dbl, _vp, _vp]),
+    'mm_stereo_product_ws_bytes': (_sz, [_i, _i64, _i, _c.POINTER(_c.c_int32)]),
+    'mm_stereo_product_pdist_fwd': (_i, [_i, _vp, _i, _i64, _i64, _i64, _vp, _vp]),
+    'mm_stereo_product_loss': (_i, [_i, _i, _vp, _i, _vp, _i64, _i64, _i64, _dbl, _dbl, _i, _vp, _vp, _vp, _vp]),
     'mm_mat_rsgd_step': (_i, [_i, _i, _i, _vp, _vp, _i64, _i, _i, _dbl, _dbl, _i, _vp, _vp]),
     'mm_mat_rsgd_momentum_step': (_i, [_i, _i, _i, _vp, _vp, _vp, _i64, _i, _i, _dbl, _dbl, _dbl, _dbl, _i, _vp, _vp]),
 }
@@ -138,6 +141,22 @@ VEC_EGRAD2RGRAD, VEC_PROJU, VEC_EXP, VEC_RETR, VEC_PROJX, VEC_TRANSP, VEC_LOG = 
 STEREO_C_FREE, STEREO_C_POSITIVE, STEREO_C_NEGATIVE = range(3)  # MM_STEREO_C_*
 (STEREO_EGRAD2RGRAD, STEREO_PROJU, STEREO_EXP, STEREO_EXP_NOPROJECT, STEREO_RETR, STEREO_PROJX, STEREO_LOG,
  STEREO_TRANSP) = range(8)  # MM_STEREO_*
+LOSS_NONE = 0  # MM_LOSS_NONE: the pair kernel reads the upstream gradient where the others read the target
+
+
+class StereoFactor(_c.Structure):
+    """mm_stereo_factor: one factor of mm_stereo_product_* (host memory, passed to the kernels by value)"""
+    _fields_ = [('x', _vp), ('c_raw', _vp), ('grad_x', _vp), ('grad_c', _vp), ('c_min', _dbl), ('m', _c.c_int32),
+                ('c_mode', _c.c_int32)]
+
+
+def stereo_factors(entries):
+    """Host array of mm_stereo_factor from (x, c_raw, grad_x, grad_c, c_min, m, c_mode) tuples of tensors (or None) and numbers."""
+    arr = (StereoFactor * len(entries))()
+    for k, (x, c_raw, gx, gc, c_min, m, mode) in enumerate(entries):
+        arr[k] = StereoFactor(None if x is None else x.data_ptr(), None if c_raw is None else c_raw.data_ptr(),
+                              None if gx is None else gx.data_ptr(), None if gc is None else gc.data_ptr(), c_min, m, mode)
+    return arr
 
 
 class BackendError(RuntimeError):

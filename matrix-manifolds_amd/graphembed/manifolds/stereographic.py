@@ -5,6 +5,8 @@ ball for c > 0, the stereographic projection of the sphere for c < 0, K = -c.
 The kernels read the raw curvature parameter from device memory and apply `get_c` themselves; `pdist` / `dist` return
 gradients for the points AND for `self.c`.  Under the overlay the name `Universal` keeps resolving to the checkout's class
 (this module defines none of that name); `Stereographic.from_universal(obj)` adopts such an instance's state."""
+import ctypes
+
 import torch
 from torch.nn.functional import softplus
 
@@ -90,6 +92,106 @@ class _StereoDist(torch.autograd.Function):
             B.lib().call('mm_stereo_dist', B.dtype_code(xc), B.ptr(xc), B.ptr(yc), B.ptr(g), cnt, m, int(squared), B.ptr(cr), mode,
                          c_min, None, B.ptr(gx), B.ptr(gy), B.ptr(gc), B.ptr(ws), B.stream_of(xc))
         return gx.reshape(xs), gy.reshape(ys), gc.to(cdtype), None, None
+
+MAX_FACTORS = 8   # mm_stereo_product_*: more factors are MM_ERR_UNSUPPORTED
+
+
+def _product_call(xs, mans, kind, target, rows, spec, want_loss):
+    """mm_stereo_product_loss on detached, contiguous points: (loss [1] or None, [grad_x_k], [grad_c_k])."""
+    lib = B.lib()
+    n = xs[0].shape[0]
+    dt = B.dtype_code(xs[0])
+    dev = xs[0].device
+    curv = [_curv_args(man, xs[0]) for man in mans]
+    _, alpha, eps, terms = spec[:4]
+    dyn = spec[4] if len(spec) > 4 else None
+    with B.on_device(dev):
+        gxs = [torch.empty_like(x) for x in xs]
+        gcs = torch.empty(len(xs), dtype=xs[0].dtype, device=dev)
+        loss = torch.empty(1, dtype=xs[0].dtype, device=dev) if want_loss else None
+        ms = (ctypes.c_int32 * len(xs))(*[x.shape[1] for x in xs])
+        ws = torch.empty(lib.raw('mm_stereo_product_ws_bytes')(dt, n, len(xs), ms), dtype=torch.uint8, device=dev)
+        fs = B.stereo_factors([(x, cr, gx, gcs[k:k + 1], c_min, x.shape[1], mode)
+                               for k, (x, gx, (cr, mode, c_min)) in enumerate(zip(xs, gxs, curv))])
+        lib.call('mm_stereo_product_loss', dt, kind, fs, len(xs), B.ptr(target), n, rows[0], rows[1], alpha, eps, terms,
+                 B.dyn_ptr(dyn, xs[0]), B.ptr(loss), B.ptr(ws), B.stream_of(xs[0]))
+    return loss, gxs, [gcs[k:k + 1] for k in range(len(xs))]
+
+
+class _StereoProductPdist(torch.autograd.Function):
+    """sum_k pdist_k(x_k, squared=True) of a product of Stereographic factors: one forward launch for all factors
+    (mm_stereo_product_pdist_fwd) and one pair pass for every gradient (mm_stereo_product_loss with MM_LOSS_NONE)."""
+
+    @staticmethod
+    def forward(ctx, mans, rows, *params):
+        k = len(mans)
+        B.require_gpu(*params[:k])
+        xs = [x.detach().contiguous() for x in params[:k]]
+        n = xs[0].shape[0]
+        curv = [_curv_args(man, xs[0]) for man in mans]
+        npairs = B.pair_offset(n, rows[1]) - B.pair_offset(n, rows[0])
+        with B.on_device(xs[0].device):
+            out = torch.empty(npairs, dtype=xs[0].dtype, device=xs[0].device)
+            fs = B.stereo_factors([(x, cr, None, None, c_min, x.shape[1], mode) for x, (cr, mode, c_min) in zip(xs, curv)])
+            B.lib().call('mm_stereo_product_pdist_fwd', B.dtype_code(xs[0]), fs, k, n, rows[0], rows[1], B.ptr(out), B.stream_of(xs[0]))
+        ctx.save_for_backward(*xs, *[cr for cr, _, _ in curv])
+        ctx.args = (mans, rows, [c.dtype for c in params[k:]])
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        mans, rows, cdtypes = ctx.args
+        k = len(mans)
+        xs = list(ctx.saved_tensors[:k])
+        # (the saved c_raw copies are the forward's curvatures: the kernels read them, not man.c, in the backward)
+        held = [_Held(man, cr) for man, cr in zip(mans, ctx.saved_tensors[k:])]
+        _, gxs, gcs = _product_call(xs, held, B.LOSS_NONE, g.contiguous(), rows, (None, 1.0, 0.0, 0), False)
+        return (None, None, *gxs, *[gc.to(dt) for gc, dt in zip(gcs, cdtypes)])
+
+
+class _Held:
+    """a manifold's curvature mode with a saved c_raw in place of the live parameter (what `_curv_args` reads)"""
+
+    def __init__(self, man, c):
+        self.c, self.sign, self.c_min = c, man.sign, man.c_min
+
+
+class _StereoProductLoss(torch.autograd.Function):
+    """The objective of a product of Stereographic factors in one pair pass (mm_stereo_product_loss): the loss and the
+    gradients of every x_k and every curvature; `spec` comes from `objective_fn.fused_spec(epoch=, alpha=)`."""
+
+    @staticmethod
+    def forward(ctx, mans, rows, spec, target, *params):
+        k = len(mans)
+        B.require_gpu(*params[:k])
+        xs = [x.detach().contiguous() for x in params[:k]]
+        n = xs[0].shape[0]
+        npairs = B.pair_offset(n, rows[1]) - B.pair_offset(n, rows[0])
+        tc = target.detach().to(xs[0].dtype).contiguous()
+        if tc.numel() != npairs:
+            raise ValueError(f'target has {tc.numel()} entries, the pair range has {npairs}')
+        kind = B.LOSS_STRESS if spec[0] == 'stress' else B.LOSS_QUOTIENT
+        loss, gxs, gcs = _product_call(xs, mans, kind, tc, rows, spec, True)
+        ctx.grads = gxs + [gc.to(c.dtype) for gc, c in zip(gcs, params[k:])]
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, up):
+        return (None, None, None, None, *B.take_grads(ctx, up, 'grads'))
+
+
+def product_pdist(mans, xs, rows=None):
+    """The summed squared pair distances of the factors (`mans[k]` on `xs[k]`), differentiable in every x_k and man.c."""
+    n = xs[0].shape[0]
+    rb, re = (0, n) if rows is None else rows
+    return _StereoProductPdist.apply(tuple(mans), (int(rb), int(re)), *xs, *[man.c for man in mans])
+
+
+def product_loss(mans, xs, target, spec, rows=None):
+    """The fused objective of the product; see _StereoProductLoss."""
+    n = xs[0].shape[0]
+    rb, re = (0, n) if rows is None else rows
+    return _StereoProductLoss.apply(tuple(mans), (int(rb), int(re)), tuple(spec), target, *xs, *[man.c for man in mans])
 
 
 class Stereographic(Manifold, torch.nn.Module):

@@ -558,14 +558,35 @@ class StereographicProductEmbedding(torch.nn.Module):
         for x, man in zip(self.xs, self.manifolds):
             man.stabilize_(x, self.r_max)
 
+    # the fused multi-factor kernels (mm_stereo_product_*): one forward launch and one pair pass for all factors; False restores
+    # the per-factor route (mm_stereo_pdist_fwd / _bwd per factor, the loss as element-wise torch passes) everywhere
+    pair_kernel = True
+
+    def _fused(self):
+        from graphembed.manifolds.stereographic import MAX_FACTORS
+        return self.pair_kernel and self.xs[0].is_cuda and self.n_components <= MAX_FACTORS
+
     def compute_dists(self, indices=None, validated=False):
         if indices is not None and not validated:
             indices = normalise_indices(indices, self.n)
-        return sum(man.pdist(take_rows(x, indices, validated=True), squared=True) for man, x in zip(self.manifolds, self.xs))
+        xs = [take_rows(x, indices, validated=True) for x in self.xs]
+        if self.n_components >= 2 and self._fused():
+            from graphembed.manifolds.stereographic import product_pdist
+            return product_pdist(self.manifolds, xs)
+        return sum(man.pdist(x, squared=True) for man, x in zip(self.manifolds, xs))
 
-    def fused_objective(self, objective_fn, gdists, i=None, **kwargs):
-        """No fused multi-factor objective kernel yet: BatchedObjective takes `objective_fn(gdists, compute_dists(i))`."""
-        return None
+    def fused_objective(self, objective_fn, gdists, i=None, rows=None, validated=False, **kwargs):
+        """`objective_fn(gdists, self.compute_dists(i), **kwargs)` and its gradients by ONE pair pass over all factors
+        (mm_stereo_product_loss), or None when there is no such kernel: a loss without `fused_spec` (SNE), CPU tensors, more
+        than 8 factors, `pair_kernel = False`.  A node minibatch `i` gathers its rows with `take_rows`: gradients outside the
+        batch are exactly zero.  `rows` selects the pair-list slice of one shard."""
+        if not hasattr(objective_fn, 'fused_spec') or gdists is None or not self._fused():
+            return None
+        from graphembed.manifolds.stereographic import product_loss
+        if i is not None and not validated:
+            i = normalise_indices(i, self.n)
+        xs = [take_rows(x, i, validated=True) for x in self.xs]
+        return product_loss(self.manifolds, xs, gdists, objective_fn.fused_spec(**kwargs), rows=rows)
 
     def __len__(self):
         return self.n

@@ -117,21 +117,26 @@ def stereo_pdist_case(m, n, dtype):
     return {'n': n, 'pairs': P, 'dtype': str(dtype).split('.')[-1], 'fwd_us': fwd, 'fwd_bwd_us': tot, 'pairs_per_s': P / (tot * 1e-6)}
 
 
-def stereo_step_case(ds, n, dtype, graph=False):
-    """training step of a product of constant-curvature factors (StereographicProductEmbedding): compute_dists + stress loss +
-    backward + fused RSGD step of the points + SGD step of the curvatures + stabilize"""
+def stereo_step_case(ds, n, dtype, graph=False, fused=False, quotient=False):
+    """training step of a product of constant-curvature factors (StereographicProductEmbedding): objective (stress, or the
+    quotient loss at epoch 1) + backward + fused RSGD step of the points + SGD step of the curvatures + stabilize.  `fused`: the
+    multi-factor pair kernel (mm_stereo_product_loss, one pair pass for all factors); otherwise the per-factor route
+    (`pair_kernel = False`: one pdist forward and backward per factor, the loss as element-wise torch passes)"""
     from graphembed.modules import StereographicProductEmbedding
+    from graphembed.objectives import QuotientLoss
     torch.manual_seed(0)
     emb = StereographicProductEmbedding(n, ds).to(device='cuda', dtype=dtype)
+    emb.pair_kernel = fused
     P = n * (n - 1) // 2
     target = torch.rand(P, dtype=dtype, device='cuda') * 0.99 + 0.01
-    fn = StressLoss()
+    fn = QuotientLoss() if quotient else StressLoss()
+    kw = dict(epoch=1, alpha=1.0) if quotient else {}
     opt = RiemannianSGD([dict(params=list(emb.xs), lr=1e-3, exact=True, max_grad_norm=20),
                          dict(params=list(emb.curvature_params), lr=1e-4, exact=False, max_grad_norm=None)], lr=1e-3)
 
     def step():
         opt.zero_grad(set_to_none=True)
-        loss = fn(target, emb.compute_dists(None))
+        loss = emb.fused_objective(fn, target, None, **kw) if fused else fn(target, emb.compute_dists(None), **kw)
         loss.backward(unit_seed(loss))
         opt.step()
         emb.stabilize()
@@ -242,6 +247,13 @@ CASES = {
     'lorentz5_n1025_f32_valu': lambda: pdist_case(_valu(M.Lorentz(5)), 1025, torch.float32),
     'stereo5x5_step_n1025_f32': lambda: stereo_step_case([5, 5], 1025, torch.float32),
     'stereo5x5_step_n1025_f32_graph': lambda: stereo_step_case([5, 5], 1025, torch.float32, graph=True),
+    # the same steps through the fused multi-factor objective kernel (mm_stereo_product_loss), and their per-factor twins
+    'stereo5x5_step_n1025_f32_fused': lambda: stereo_step_case([5, 5], 1025, torch.float32, fused=True),
+    'stereo5x5_step_n1025_f32_fused_graph': lambda: stereo_step_case([5, 5], 1025, torch.float32, fused=True, graph=True),
+    'stereo2x8_step_n4039_f32': lambda: stereo_step_case([2] * 8, 4039, torch.float32),
+    'stereo2x8_step_n4039_f32_fused': lambda: stereo_step_case([2] * 8, 4039, torch.float32, fused=True),
+    'stereo5x5_quotient_step_n1025_f32': lambda: stereo_step_case([5, 5], 1025, torch.float32, quotient=True),
+    'stereo5x5_quotient_step_n1025_f32_fused': lambda: stereo_step_case([5, 5], 1025, torch.float32, fused=True, quotient=True),
     'lorentz5x5_step_n1025_f32': lambda: step_case([M.Lorentz(5), M.Lorentz(5)], 1025, torch.float32),
     'c4_csphd_sne_incl_step_f32_graph': lambda: step_case([M.Lorentz(6), M.Sphere(6), M.SymmetricPositiveDefinite(2)], 1025, torch.float32, sne='incl', graph=True),
 }
