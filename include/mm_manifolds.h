@@ -153,7 +153,7 @@ int mm_spd_pdist_loss(int dtype, int loss_kind, const void* x, const void* targe
  *            the buffers; repeated indices break the "each gradient row is written once" contract silently.  The Python
  *            layer checks host-side index tensors (graphembed.modules.distinct_in_range); device-side ones are the
  *            caller's responsibility.  The same holds for mm_vec_pdist_loss_subset, mm_product_pairs_loss_subset,
- *            mm_pair_gather and mm_train_step.batch_idx. */
+ *            mm_stereo_product_loss_subset, mm_pair_gather and mm_train_step.batch_idx. */
 int mm_spd_pdist_loss_subset(int dtype, int loss_kind, const void* x, const void* dense, const void* scale_raw,
                              int64_t n_total, int d, const int64_t* idx, int64_t bs, int64_t row_begin, int64_t row_end,
                              double alpha, double eps, int terms, const double* loss_params, double wmin, double wmax,
@@ -478,6 +478,22 @@ int mm_stereo_map(int dtype, int op, const void* x, const void* u, const void* y
  * project(x - lr r).  x_new may equal x. */
 int mm_stereo_rsgd_step(int dtype, const void* x, const void* egrad, int64_t cnt, int m, const void* c_raw, int c_mode,
                         double c_min, double lr, double max_grad_norm, int exact, void* x_new, mm_stream_t stream);
+/* Fused RiemannianAdam update (optim/radam.py:62-98 of the reference on Universal) in one launch, one thread per point:
+ *   r = egrad / lambda_c(x)^2;  nrm = lambda_1(x) |r|  (Universal.norm: the conformal factor at c = 1, clamped at 1e-15, as in
+ *   mm_stereo_rsgd_step);  exp_avg_sq = beta2 exp_avg_sq + (1 - beta2) nrm^2  (ONE scalar per point, the norm BEFORE clipping,
+ *   stored broadcast over the point's m entries);  r *= min(max_grad_norm / nrm, 1) if max_grad_norm > 0 (a zero gradient stays
+ *   zero);  exp_avg = beta1 exp_avg + (1 - beta1) r;  u = -alpha exp_avg / (sqrt(exp_avg_sq) + eps) with
+ *   alpha = lr sqrt(1 - beta2^t) / (1 - beta1^t) and, if nc, beta2 = 1 - 1 / t (AdamNc);
+ *   x_new = exact ? project(exp_x(u)) : project(x + u);  exp_avg = transp(x -> x_new, exp_avg), MM_STEREO_TRANSP's arithmetic.
+ * 1 - beta1 and 1 - beta2 are formed in fp64 from the fp64 arguments and then rounded to `dtype`, as the reference forms them.
+ * exp_avg / exp_avg_sq [cnt, m] are updated IN PLACE; x_new may equal x.  `step` (device fp64 scalar t >= 1, state['step'])
+ * is read by every workgroup and advanced by the last one through `ticket` (device counter, zero between launches), as
+ * mm_vec_radam_step does: a captured graph keeps counting.  Argument errors as mm_stereo_rsgd_step; step and ticket must
+ * not be NULL. */
+int mm_stereo_radam_step(int dtype, const void* x, const void* egrad, void* exp_avg, void* exp_avg_sq, double* step,
+                         unsigned* ticket, int64_t cnt, int m, const void* c_raw, int c_mode, double c_min, double lr,
+                         double beta1, double beta2, int nc, double eps, double max_grad_norm, int exact, void* x_new,
+                         mm_stream_t stream);
 /* products/embedding.py:37-46 in one launch: x / max(|x| / r_max, 1), then projx.  x_new may equal x. */
 int mm_stereo_stabilize(int dtype, const void* x, int64_t cnt, int m, const void* c_raw, int c_mode, double c_min,
                         double r_max, void* x_new, mm_stream_t stream);
@@ -516,6 +532,25 @@ int mm_stereo_product_loss(int dtype, int loss_kind, const mm_stereo_factor* f, 
                            int64_t row_begin, int64_t row_end, double alpha, double eps, int terms,
                            const double* loss_params, void* loss_out /* [1]; may be NULL for MM_LOSS_NONE */, void* ws,
                            mm_stream_t stream);
+/* mm_stereo_product_loss for a NODE MINIBATCH, the counterpart of mm_spd_pdist_loss_subset: f[k].x is the FULL table
+ * [n_total, m_k], the step's bs points are its rows idx[0 .. bs) (device int64, distinct, any order; see the paragraph on `idx`
+ * at mm_spd_pdist_loss_subset), the target of batch pair (a, b), a < b, is dense[idx[a]][idx[b]] (dense: contiguous
+ * [n_total, n_total] of `dtype`), row_begin / row_end shard the pair list of the BATCH (0 <= row_begin <= row_end <= bs).
+ * f[k].grad_x [n_total, m_k] is OVERWRITTEN: rows idx[.] with this shard's partial gradient, every other row with exact zeros;
+ * f[k].grad_c [1] and loss_out [1] as above.  MM_LOSS_STRESS and MM_LOSS_QUOTIENT only (an upstream gradient per pair has no
+ * dense form: MM_LOSS_NONE is MM_ERR_ARG).  The pair tiles run over batch positions with the arithmetic, the tile shape and the
+ * summation order of mm_stereo_product_loss: the result is BITWISE that of mm_stereo_product_loss on the gathered tables
+ * x_k[idx] with the condensed targets of the same pairs.  Four launches whatever nf is: one that clears the gradient tables,
+ * the pair kernel, the finalize over (batch position, factor), the reduction.
+ * ws: mm_stereo_product_ws_bytes(dtype, bs, nf, m) - the BATCH's size; it needs no clearing.
+ * Limits and error order as above with n = bs (nf <= 8, m <= 16, bs <= 32768); bs > n_total, bs < 0, a null idx or dense are
+ * MM_ERR_ARG, n_total >= 2^31 is MM_ERR_UNSUPPORTED.  bs < 2 or a range without pairs writes zero gradients, zero grad_c and a
+ * zero loss.  No float atomics, nothing allocated, no synchronisation: capturable, and the contents of idx may change between
+ * replays. */
+int mm_stereo_product_loss_subset(int dtype, int loss_kind, const mm_stereo_factor* f, int nf, const void* dense,
+                                  int64_t n_total, const int64_t* idx, int64_t bs, int64_t row_begin, int64_t row_end,
+                                  double alpha, double eps, int terms, const double* loss_params, void* loss_out, void* ws,
+                                  mm_stream_t stream);
 
 /* ---- product embeddings ---------------------------------------------------- */
 /* Objective of a product embedding in one pass over the pair vectors (the element-wise part of

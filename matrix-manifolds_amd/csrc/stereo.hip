@@ -26,9 +26,11 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstdint>
 #include <type_traits>
 
 #include "../../include/mm_manifolds.h"
+#include "adam.hpp"
 #include "loss.hpp"
 
 namespace mm {
@@ -585,6 +587,62 @@ __global__ __launch_bounds__(kPtBlk) void stabilize_kernel(const T* __restrict__
   store_vec(out, row, m, project(xv, c));
 }
 
+// Riemannian Adam (optim/radam.py:62-98 of the reference on Universal), one thread per point: the Riemannian gradient, its norm
+// (the second moment: ONE scalar per point, before clipping, stored broadcast over the point), clipping, both moments, the
+// bias-corrected direction, exp / retr, and the transport of the first moment to the new point in map_kernel's gyration form.
+template <typename T>
+__global__ __launch_bounds__(kPtBlk) void radam_kernel(const T* __restrict__ x, const T* __restrict__ eg, T* __restrict__ exp_avg,
+                                                       T* __restrict__ exp_avg_sq, int64_t cnt, int m, const T* __restrict__ c_raw,
+                                                       int c_mode, double c_min, AdamArgs<T> a, double beta1_64, double beta2_64,
+                                                       T* __restrict__ out) {
+  const int64_t row = int64_t(blockIdx.x) * kPtBlk + threadIdx.x;
+  // the step's coefficients once per workgroup, through LDS: the two fp64 pow() stay out of the per-point code, whose `k < m`
+  // masks fill the scalar registers
+  // 1 - beta is formed in fp64 from the caller's fp64 betas, as the reference forms it on the host: 1 - float(0.99) is 1e-6 off 0.01
+  __shared__ T coef[4];
+  if (threadIdx.x == 0) {
+    adam_coeffs(a, coef[0], coef[1]);
+    coef[2] = T(a.nc ? 1.0 / *a.step : 1.0 - beta2_64);
+    coef[3] = T(1.0 - beta1_64);
+  }
+  __syncthreads();
+  const T beta2 = coef[0], alpha = coef[1], omb2 = coef[2], omb1 = coef[3];
+  if (row < cnt) {
+    const T c = load_curv(c_raw, c_mode, c_min).c;
+    const Vec<T> xv = load_vec(x, row, m), ev = load_vec(eg, row, m);
+    Vec<T> mo = load_vec(exp_avg, row, m);
+    const T h = conf_den(xv, c) * T(0.5), f = h * h;          // egrad2rgrad
+    Vec<T> r;
+#pragma unroll
+    for (int k = 0; k < kMaxDim; ++k) r.v[k] = f * ev.v[k];
+    // Universal.norm: the conformal factor at c = 1, as in rsgd_kernel
+    const T nrm = 2 / conf_den(xv, T(1)) * M<T>::sqrt(dot(r, r));
+    const T v = beta2 * exp_avg_sq[row * m] + omb2 * (nrm * nrm);
+    const T clip = a.max_grad_norm > 0 ? fmin(a.max_grad_norm / nrm, T(1)) : T(1);   // (nrm = 0: min(inf, 1) = 1, the zero gradient stays)
+    const T s = -alpha / (M<T>::sqrt(v) + a.eps);
+    Vec<T> dir, vv;
+#pragma unroll
+    for (int k = 0; k < kMaxDim; ++k) {
+      mo.v[k] = a.beta1 * mo.v[k] + omb1 * (r.v[k] * clip);
+      dir.v[k] = mo.v[k] * s;
+      vv.v[k] = v;
+    }
+    const Vec<T> yv = a.exact ? project(expmap(xv, dir, c), c) : project(axpby(T(1), xv, T(1), dir), c);
+    // gyr[y, -x] exp_avg lambda_x / lambda_y, the arithmetic of MM_STEREO_TRANSP
+    const Vec<T> gv = neg(xv);
+    const T u2 = dot(yv, yv), v2 = dot(gv, gv), uvd = dot(yv, gv), uw = dot(yv, mo), vw = dot(gv, mo), cc = c * c;
+    const T ga = -cc * uw * v2 + c * vw + 2 * cc * uvd * vw, gb = -cc * vw * u2 - c * uw;
+    const T d = fmax(1 + 2 * c * uvd + cc * u2 * v2, T(kMinNorm));
+    const T ratio = conf_den(yv, c) / conf_den(xv, c);
+#pragma unroll
+    for (int k = 0; k < kMaxDim; ++k) mo.v[k] = (mo.v[k] + 2 * (ga * yv.v[k] + gb * gv.v[k]) / d) * ratio;
+    store_vec(out, row, m, yv);
+    store_vec(exp_avg, row, m, mo);
+    store_vec(exp_avg_sq, row, m, vv);
+  }
+  adam_tick(a.step, a.ticket, gridDim.x);
+}
+
 // ---- host -----------------------------------------------------------------------------------------------------------------
 inline int status() {
   const hipError_t e = hipGetLastError();
@@ -726,9 +784,18 @@ __global__ __launch_bounds__(kC* kWaves) void product_fwd_kernel(PFactors<T> pf,
   }
 }
 
-template <typename T, int MP, int LOSS>
-__global__ __launch_bounds__(kC* kWaves) void product_loss_kernel(PFactors<T> pf, const T* __restrict__ target, int n, int rb, int re,
-                                                                  int bi0, int nbr, LossArgs<T> la, double* __restrict__ partials) {
+// node id of batch position `pos`: the low 32 bits of the index, clamped into the table
+__device__ __forceinline__ int node_of(const int64_t* __restrict__ idx, int pos, int n_total) {
+  return min(max(int(idx[pos]), 0), n_total - 1);
+}
+
+// The tile body of product_loss_kernel.  SUB: a node minibatch - n counts the batch's POSITIONS, the tiles, records and
+// partials are laid out over them exactly as over nodes, and only the point loads (row idx[pos] of the full table) and the
+// target load (dense[idx[i]][idx[j]], `target` being the dense [n_total, n_total] matrix) go through idx.
+template <typename T, int MP, int LOSS, bool SUB>
+__device__ __forceinline__ void product_loss_tile(const PFactors<T>& pf, const T* __restrict__ target, const int64_t* __restrict__ idx,
+                                                  int n_total, int n, int rb, int re, int bi0, int nbr, LossArgs<T> la,
+                                                  double* __restrict__ partials) {
   constexpr int TR = Tile<T>::rows, RW = TR / kWaves, CW = kC / kWaves, LD = kC + 1, UNR = sizeof(T) == 4 ? 2 : 1, KUN = sizeof(T) == 4 ? MP : 4;
   const int bj = blockIdx.x, bi = bi0 + blockIdx.y;
   const int slot_p = blockIdx.y * gridDim.x + blockIdx.x, tiles = gridDim.x * gridDim.y;
@@ -748,7 +815,8 @@ __global__ __launch_bounds__(kC* kWaves) void product_loss_kernel(PFactors<T> pf
   // a factor's points of the tile: rows, columns and their squared norms
   auto load_points = [&](const T* __restrict__ x, int m) {
     if (tid < TR) {
-      const int i = min(bi * TR + tid, n - 1);
+      int i = min(bi * TR + tid, n - 1);
+      if constexpr (SUB) i = node_of(idx, i, n_total);
       T a = 0;
 #pragma unroll
       for (int k = 0; k < MP; ++k) {
@@ -759,7 +827,8 @@ __global__ __launch_bounds__(kC* kWaves) void product_loss_kernel(PFactors<T> pf
       sar[tid] = a;
     }
     if (wave == 1) {
-      const int jc = min(j, n - 1);
+      int jc = min(j, n - 1);
+      if constexpr (SUB) jc = node_of(idx, jc, n_total);
       T b = 0;
 #pragma unroll
       for (int k = 0; k < MP; ++k) {
@@ -808,12 +877,19 @@ __global__ __launch_bounds__(kC* kWaves) void product_loss_kernel(PFactors<T> pf
   }
   loss_resolve<T, LOSS>(la);
   const int64_t base = poff(n, rb);
+  size_t tcol = 0;                     // SUB: the lane's column of the dense matrix
+  if constexpr (SUB) tcol = size_t(node_of(idx, min(j, n - 1), n_total));
   T lacc = 0;
 #pragma unroll
   for (int r = 0; r < RW; ++r) {
     const int i = bi * TR + wave * RW + r;
     const bool live = j > i && j < n && i >= rb && i < re;
-    const T tg = live ? target[poff(n, i) - base + (j - i - 1)] : T(1);
+    T tg = T(1);
+    if constexpr (SUB) {
+      if (live) tg = target[size_t(node_of(idx, min(i, n - 1), n_total)) * size_t(n_total) + tcol];
+    } else {
+      tg = live ? target[poff(n, i) - base + (j - i - 1)] : T(1);
+    }
     if constexpr (LOSS == MM_LOSS_NONE) {
       gr[r] = live ? tg : T(0);
     } else {
@@ -920,9 +996,25 @@ __global__ __launch_bounds__(kC* kWaves) void product_loss_kernel(PFactors<T> pf
   }
 }
 
-// grad_x of factor blockIdx.y: a node's records in slot order, as pdist_bwd_finalize_kernel adds them
-template <typename T>
-__global__ __launch_bounds__(256) void product_finalize_kernel(PFactors<T> pf, int n, int rb, int re, int nbr, int nbc) {
+template <typename T, int MP, int LOSS>
+__global__ __launch_bounds__(kC* kWaves) void product_loss_kernel(PFactors<T> pf, const T* __restrict__ target, int n, int rb, int re,
+                                                                  int bi0, int nbr, LossArgs<T> la, double* __restrict__ partials) {
+  product_loss_tile<T, MP, LOSS, false>(pf, target, nullptr, 0, n, rb, re, bi0, nbr, la, partials);
+}
+
+// the same pair pass over the bs positions of a node minibatch (mm_stereo_product_loss_subset)
+template <typename T, int MP, int LOSS>
+__global__ __launch_bounds__(kC* kWaves) void subset_loss_kernel(PFactors<T> pf, const T* __restrict__ dense, const int64_t* __restrict__ idx,
+                                                                 int n_total, int bs, int rb, int re, int bi0, int nbr, LossArgs<T> la,
+                                                                 double* __restrict__ partials) {
+  product_loss_tile<T, MP, LOSS, true>(pf, dense, idx, n_total, bs, rb, re, bi0, nbr, la, partials);
+}
+
+// grad_x of factor blockIdx.y: a node's records in slot order, as pdist_bwd_finalize_kernel adds them (SUB: the records of batch
+// position v, the point and the gradient row idx[v] of the full table)
+template <typename T, bool SUB>
+__device__ __forceinline__ void product_finalize_node(const PFactors<T>& pf, const int64_t* __restrict__ idx, int n_total, int n, int rb,
+                                                      int re, int nbr, int nbc) {
   constexpr int TR = Tile<T>::rows;
   const int v = blockIdx.x * 256 + threadIdx.x;
   if (v >= n) return;
@@ -958,9 +1050,29 @@ __global__ __launch_bounds__(256) void product_finalize_kernel(PFactors<T> pf, i
 #pragma unroll
   for (int k = 0; k <= kMaxDim; ++k)
     if (k == m) vs = acc[k];
+  int row = v;
+  if constexpr (SUB) row = node_of(idx, v, n_total);
 #pragma unroll
   for (int k = 0; k < kMaxDim; ++k)
-    if (k < m) grad[size_t(v) * m + k] = acc[k] + vs * x[size_t(v) * m + k];
+    if (k < m) grad[size_t(row) * m + k] = acc[k] + vs * x[size_t(row) * m + k];
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void product_finalize_kernel(PFactors<T> pf, int n, int rb, int re, int nbr, int nbc) {
+  product_finalize_node<T, false>(pf, nullptr, 0, n, rb, re, nbr, nbc);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void subset_finalize_kernel(PFactors<T> pf, const int64_t* __restrict__ idx, int n_total, int bs, int rb,
+                                                              int re, int nbr, int nbc) {
+  product_finalize_node<T, true>(pf, idx, n_total, bs, rb, re, nbr, nbc);
+}
+
+// exact zeros in every gradient table of a minibatch step (factor blockIdx.y): the rows outside the batch keep them
+template <typename T> __global__ __launch_bounds__(256) void subset_clear_kernel(PFactors<T> pf, int64_t n_total) {
+  const PFactor<T>& F = pf.f[blockIdx.y];
+  const int64_t count = n_total * F.m;
+  for (int64_t k = int64_t(blockIdx.x) * 256 + threadIdx.x; k < count; k += int64_t(gridDim.x) * 256) F.grad_x[k] = T(0);
 }
 
 // block 0: the loss; block 1 + k: grad_c of factor k = dc/dc_raw * its partials - fp64, fixed order
@@ -1075,6 +1187,54 @@ int product_loss(int loss_kind, const mm_stereo_factor* f, int nf, const T* targ
   if (n >= 1)   // (a range without pairs: the sums over no record are the zero gradients)
     product_finalize_kernel<T><<<dim3(unsigned((n + 255) / 256), unsigned(nf)), dim3(256), 0, st>>>(pf, int(n), int(rb), pairs ? int(re) : int(rb), nbr, nbc);
   product_reduce_kernel<T><<<dim3(unsigned(nf + 1)), dim3(256), 0, st>>>(pf, partials, count, nbc, bi0, loss_kind == MM_LOSS_NONE ? nullptr : loss_out);
+  return status();
+}
+
+template <typename T, int LOSS>
+void subset_loss_launch(int pad, dim3 grid, hipStream_t st, const PFactors<T>& pf, const T* dense, const int64_t* idx, int n_total, int bs,
+                        int rb, int re, int bi0, int nbr, LossArgs<T> la, double* partials) {
+  const dim3 wg(kC * kWaves);
+  switch (pad) {
+    case 4: subset_loss_kernel<T, 4, LOSS><<<grid, wg, 0, st>>>(pf, dense, idx, n_total, bs, rb, re, bi0, nbr, la, partials); break;
+    case 8: subset_loss_kernel<T, 8, LOSS><<<grid, wg, 0, st>>>(pf, dense, idx, n_total, bs, rb, re, bi0, nbr, la, partials); break;
+    default: subset_loss_kernel<T, 16, LOSS><<<grid, wg, 0, st>>>(pf, dense, idx, n_total, bs, rb, re, bi0, nbr, la, partials); break;
+  }
+}
+
+// product_loss over the batch's positions: the workspace, the tiles and the reduction are those of n = bs; one launch in front
+// clears the full-size gradient tables, the finalize writes the batch's rows - four launches whatever nf is
+template <typename T>
+int product_loss_subset(int loss_kind, const mm_stereo_factor* f, int nf, const T* dense, int64_t n_total, const int64_t* idx, int64_t bs,
+                        int64_t rb, int64_t re, double alpha, double eps, int terms, const double* loss_params, T* loss_out, void* ws,
+                        hipStream_t st) {
+  constexpr int TR = Tile<T>::rows;
+  int widest;
+  const PFactors<T> pf = product_args<T>(f, nf, bs, ws, &widest);
+  const int nbr = int((bs + TR - 1) / TR), nbc = int((bs + kC - 1) / kC);
+  size_t slabs = 0;
+  for (int k = 0; k < nf; ++k) slabs += slab_bytes(sizeof(T), bs, f[k].m);
+  double* partials = reinterpret_cast<double*>(static_cast<char*>(ws) + slabs);
+  const bool pairs = bs >= 2 && has_pairs(bs, rb, re);
+  int count = 0, bi0 = 0;
+  if (n_total >= 1) {
+    const int64_t blocks = (n_total * widest + 255) / 256;
+    subset_clear_kernel<T><<<dim3(unsigned(blocks < 4096 ? blocks : 4096), unsigned(nf)), dim3(256), 0, st>>>(pf, n_total);
+  }
+  if (pairs) {
+    bi0 = int(rb / TR);
+    const int bi1 = int((re - 1) / TR);
+    const dim3 grid(nbc, bi1 - bi0 + 1);
+    count = int(grid.x * grid.y);
+    LossArgs<T> la{nullptr, T(alpha), T(eps), terms, nullptr, loss_params};
+    const int pad = pad_of(widest);
+    if (loss_kind == MM_LOSS_STRESS)
+      subset_loss_launch<T, MM_LOSS_STRESS>(pad, grid, st, pf, dense, idx, int(n_total), int(bs), int(rb), int(re), bi0, nbr, la, partials);
+    else
+      subset_loss_launch<T, MM_LOSS_QUOTIENT>(pad, grid, st, pf, dense, idx, int(n_total), int(bs), int(rb), int(re), bi0, nbr, la, partials);
+    subset_finalize_kernel<T><<<dim3(unsigned((bs + 255) / 256), unsigned(nf)), dim3(256), 0, st>>>(pf, idx, int(n_total), int(bs), int(rb),
+                                                                                                    int(re), nbr, nbc);
+  }
+  product_reduce_kernel<T><<<dim3(unsigned(nf + 1)), dim3(256), 0, st>>>(pf, partials, count, nbc, bi0, loss_out);
   return status();
 }
 
@@ -1197,6 +1357,31 @@ int mm_stereo_rsgd_step(int dtype, const void* x, const void* egrad, int64_t cnt
   return status();
 }
 
+int mm_stereo_radam_step(int dtype, const void* x, const void* egrad, void* exp_avg, void* exp_avg_sq, double* step, unsigned* ticket,
+                         int64_t cnt, int m, const void* c_raw, int c_mode, double c_min, double lr, double beta1, double beta2, int nc,
+                         double eps, double max_grad_norm, int exact, void* x_new, mm_stream_t stream) {
+  if ((dtype != MM_F32 && dtype != MM_F64) || cnt < 0 || m < 1 || bad_curv(c_raw, c_mode, c_min) || !step || !ticket) return MM_ERR_ARG;
+  if (cnt > 0 && (!x || !egrad || !exp_avg || !exp_avg_sq || !x_new)) return MM_ERR_ARG;
+  if (m > kMaxDim || cnt > (int64_t(1) << 31) * kPtBlk - 1) return MM_ERR_UNSUPPORTED;
+  if (cnt == 0) return MM_OK;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const dim3 grid(unsigned((cnt + kPtBlk - 1) / kPtBlk)), wg(kPtBlk);
+  if (dtype == MM_F32) {
+    using T = float;
+    const mm::AdamArgs<T> a{T(lr), T(beta1), T(beta2), T(eps), T(max_grad_norm), nc, exact, step, ticket};
+    radam_kernel<T><<<grid, wg, 0, st>>>(static_cast<const T*>(x), static_cast<const T*>(egrad), static_cast<T*>(exp_avg),
+                                         static_cast<T*>(exp_avg_sq), cnt, m, static_cast<const T*>(c_raw), c_mode, c_min, a,
+                                         beta1, beta2, static_cast<T*>(x_new));
+  } else {
+    using T = double;
+    const mm::AdamArgs<T> a{T(lr), T(beta1), T(beta2), T(eps), T(max_grad_norm), nc, exact, step, ticket};
+    radam_kernel<T><<<grid, wg, 0, st>>>(static_cast<const T*>(x), static_cast<const T*>(egrad), static_cast<T*>(exp_avg),
+                                         static_cast<T*>(exp_avg_sq), cnt, m, static_cast<const T*>(c_raw), c_mode, c_min, a,
+                                         beta1, beta2, static_cast<T*>(x_new));
+  }
+  return status();
+}
+
 int mm_stereo_stabilize(int dtype, const void* x, int64_t cnt, int m, const void* c_raw, int c_mode, double c_min, double r_max,
                         void* x_new, mm_stream_t stream) {
   if ((dtype != MM_F32 && dtype != MM_F64) || cnt < 0 || m < 1 || bad_curv(c_raw, c_mode, c_min) || !(r_max > 0)) return MM_ERR_ARG;
@@ -1254,6 +1439,25 @@ int mm_stereo_product_loss(int dtype, int loss_kind, const mm_stereo_factor* f, 
                                static_cast<float*>(loss_out), ws, st);
   return product_loss<double>(loss_kind, f, nf, static_cast<const double*>(target), n, row_begin, row_end, alpha, eps, terms, loss_params,
                               static_cast<double*>(loss_out), ws, st);
+}
+
+int mm_stereo_product_loss_subset(int dtype, int loss_kind, const mm_stereo_factor* f, int nf, const void* dense, int64_t n_total,
+                                  const int64_t* idx, int64_t bs, int64_t row_begin, int64_t row_end, double alpha, double eps, int terms,
+                                  const double* loss_params, void* loss_out, void* ws, mm_stream_t stream) {
+  if (n_total < 0 || bs < 0 || bs > n_total) return MM_ERR_ARG;
+  int rc = product_check(dtype, f, nf, bs, row_begin, row_end, true);
+  if (rc == MM_ERR_ARG) return rc;
+  for (int k = 0; k < nf && k < 64; ++k)   // (the tables are cleared even when the batch is empty)
+    if (n_total >= 1 && (!f[k].x || !f[k].grad_x)) return MM_ERR_ARG;
+  if ((loss_kind != MM_LOSS_STRESS && loss_kind != MM_LOSS_QUOTIENT) || !ws || !loss_out || !idx || !dense) return MM_ERR_ARG;
+  if (n_total > INT32_MAX) rc = MM_ERR_UNSUPPORTED;   // node ids are the low 32 bits of an index
+  if (rc != MM_OK) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (dtype == MM_F32)
+    return product_loss_subset<float>(loss_kind, f, nf, static_cast<const float*>(dense), n_total, idx, bs, row_begin, row_end, alpha, eps,
+                                      terms, loss_params, static_cast<float*>(loss_out), ws, st);
+  return product_loss_subset<double>(loss_kind, f, nf, static_cast<const double*>(dense), n_total, idx, bs, row_begin, row_end, alpha, eps,
+                                     terms, loss_params, static_cast<double*>(loss_out), ws, st);
 }
 
 }  // extern "C"

@@ -127,10 +127,13 @@ SIGNATURES = {
     'mm_stereo_dist': (_i, [_i, _vp, _vp, _vp, _i64, _i, _i, _vp, _i, _dbl, _vp, _vp, _vp, _vp, _vp, _vp]),
     'mm_stereo_map': (_i, [_i, _i, _vp, _vp, _vp, _i64, _i, _vp, _i, _dbl, _vp, _vp]),
     'mm_stereo_rsgd_step': (_i, [_i, _vp, _vp, _i64, _i, _vp, _i, _dbl, _dbl, _dbl, _i, _vp, _vp]),
+    'mm_stereo_radam_step': (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _vp, _i, _dbl, _dbl, _dbl, _dbl, _i, _dbl, _dbl, _i,
+                                  _vp, _vp]),
     'mm_stereo_stabilize': (_i, [_i, _vp, _i64, _i, _vp, _i, _dbl, _dbl, _vp, _vp]),
     'mm_stereo_product_ws_bytes': (_sz, [_i, _i64, _i, _c.POINTER(_c.c_int32)]),
     'mm_stereo_product_pdist_fwd': (_i, [_i, _vp, _i, _i64, _i64, _i64, _vp, _vp]),
     'mm_stereo_product_loss': (_i, [_i, _i, _vp, _i, _vp, _i64, _i64, _i64, _dbl, _dbl, _i, _vp, _vp, _vp, _vp]),
+    'mm_stereo_product_loss_subset': (_i, [_i, _i, _vp, _i, _vp, _i64, _vp, _i64, _i64, _i64, _dbl, _dbl, _i, _vp, _vp, _vp, _vp]),
     'mm_mat_rsgd_step': (_i, [_i, _i, _i, _vp, _vp, _i64, _i, _i, _dbl, _dbl, _i, _vp, _vp]),
     'mm_mat_rsgd_momentum_step': (_i, [_i, _i, _i, _vp, _vp, _vp, _i64, _i, _i, _dbl, _dbl, _dbl, _dbl, _i, _vp, _vp]),
 }

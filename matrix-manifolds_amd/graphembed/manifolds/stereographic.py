@@ -180,6 +180,56 @@ class _StereoProductLoss(torch.autograd.Function):
         return (None, None, None, None, *B.take_grads(ctx, up, 'grads'))
 
 
+class _StereoProductSubsetLoss(torch.autograd.Function):
+    """The objective of a NODE MINIBATCH of a product of Stereographic factors inside the pair kernel
+    (mm_stereo_product_loss_subset): `params` are the FULL tables and the curvatures, `idx` addresses the tables' rows and the
+    targets dense[idx[a]][idx[b]], the gradients come back full-size with exact zeros outside the batch - no gather, no
+    scatter-add.  `cache` (a dict kept by the embedding) holds the batch-sized workspace: a captured graph refers to it."""
+
+    @staticmethod
+    def forward(ctx, mans, rows, spec, cache, idx, dense, *params):
+        k = len(mans)
+        B.require_gpu(*params[:k], dense)
+        lib = B.lib()
+        xs = [x.detach().contiguous() for x in params[:k]]
+        n_total, bs = xs[0].shape[0], idx.numel()
+        dt, dev = B.dtype_code(xs[0]), xs[0].device
+        if dense.dtype != xs[0].dtype or not dense.is_contiguous() or dense.shape != (n_total, n_total):
+            raise ValueError('dense targets must be a contiguous [n, n] matrix of the embedding\'s dtype')
+        kind = B.LOSS_STRESS if spec[0] == 'stress' else B.LOSS_QUOTIENT
+        _, alpha, eps, terms = spec[:4]
+        dyn = spec[4] if len(spec) > 4 else None
+        curv = [_curv_args(man, xs[0]) for man in mans]
+        with B.on_device(dev):
+            ic = idx.to(device=dev, dtype=torch.int64).contiguous()
+            gxs = [torch.empty_like(x) for x in xs]
+            gcs = torch.empty(k, dtype=xs[0].dtype, device=dev)
+            loss = torch.empty(1, dtype=xs[0].dtype, device=dev)
+            key = (xs[0].dtype, dev, bs)
+            ws = cache.get(key)
+            if ws is None:
+                ms = (ctypes.c_int32 * k)(*[x.shape[1] for x in xs])
+                ws = torch.empty(lib.raw('mm_stereo_product_ws_bytes')(dt, bs, k, ms), dtype=torch.uint8, device=dev)
+                cache[key] = ws
+            fs = B.stereo_factors([(x, cr, gx, gcs[j:j + 1], c_min, x.shape[1], mode)
+                                   for j, (x, gx, (cr, mode, c_min)) in enumerate(zip(xs, gxs, curv))])
+            lib.call('mm_stereo_product_loss_subset', dt, kind, fs, k, B.ptr(dense), n_total, B.ptr(ic), bs, rows[0], rows[1],
+                     alpha, eps, terms, B.dyn_ptr(dyn, xs[0]), B.ptr(loss), B.ptr(ws), B.stream_of(xs[0]))
+        ctx.grads = gxs + [gcs[j:j + 1].to(c.dtype) for j, c in enumerate(params[k:])]
+        return loss[0]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, up):
+        return (None, None, None, None, None, None, *B.take_grads(ctx, up, 'grads'))
+
+
+def product_loss_subset(mans, xs, idx, dense, spec, cache, rows=None):
+    """The fused objective of the node minibatch `idx` of the product; see _StereoProductSubsetLoss."""
+    rb, re = (0, idx.numel()) if rows is None else rows
+    return _StereoProductSubsetLoss.apply(tuple(mans), (int(rb), int(re)), tuple(spec), cache, idx, dense, *xs, *[man.c for man in mans])
+
+
 def product_pdist(mans, xs, rows=None):
     """The summed squared pair distances of the factors (`mans[k]` on `xs[k]`), differentiable in every x_k and man.c."""
     n = xs[0].shape[0]
@@ -312,6 +362,29 @@ class Stereographic(Manifold, torch.nn.Module):
             B.lib().call('mm_stereo_rsgd_step', B.dtype_code(xc), B.ptr(xc), B.ptr(gc), xc.shape[0], self.n, B.ptr(cr), mode, c_min,
                          float(lr), -1.0 if max_grad_norm is None else float(max_grad_norm), int(bool(exact)), B.ptr(out),
                          B.stream_of(xc))
+        return x if inplace else out.reshape(x.shape)
+
+    def radam_step(self, x, egrad, exp_avg, exp_avg_sq, step, ticket, *, lr, betas, nc, eps, max_grad_norm=None, exact=False,
+                   inplace=False):
+        """Fused RiemannianAdam update (optim/radam.py:62-98 of the reference) in one launch (mm_stereo_radam_step): moments
+        updated in place, `step` (device fp64 scalar) advanced by the kernel; returns the new points (`x` itself when
+        `inplace`), or None when the tensors are not eligible (CPU tensors, non-contiguous or mistyped moments)."""
+        ok = (x.is_cuda and x.dtype in (torch.float32, torch.float64) and x.numel() > 0 and x.shape[-1] == self.n
+              and exp_avg.is_contiguous() and exp_avg_sq.is_contiguous() and exp_avg.dtype == x.dtype
+              and exp_avg_sq.dtype == x.dtype and exp_avg.shape == x.shape and exp_avg_sq.shape == x.shape)
+        if not ok:
+            return None
+        xd = x.detach()
+        inplace = inplace and xd.is_contiguous()
+        xc = xd.reshape(-1, self.n).contiguous()
+        gc = egrad.detach().reshape(-1, self.n).to(xc.dtype).contiguous()
+        cr, mode, c_min = _curv_args(self, xc)
+        with B.on_device(xc.device):
+            out = xc if inplace else torch.empty_like(xc)
+            B.lib().call('mm_stereo_radam_step', B.dtype_code(xc), B.ptr(xc), B.ptr(gc), B.ptr(exp_avg), B.ptr(exp_avg_sq),
+                         B.ptr(step), B.ptr(ticket), xc.shape[0], self.n, B.ptr(cr), mode, c_min, float(lr), float(betas[0]),
+                         float(betas[1] if betas[1] is not None else 0.0), int(bool(nc)), float(eps),
+                         -1.0 if max_grad_norm is None else float(max_grad_norm), int(bool(exact)), B.ptr(out), B.stream_of(xc))
         return x if inplace else out.reshape(x.shape)
 
     @torch.no_grad()

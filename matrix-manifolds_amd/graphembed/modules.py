@@ -514,6 +514,9 @@ class BatchedObjective(torch.nn.Module):
         return self.objective_fn(gdists, self.embedding.compute_dists(indices, validated=True), *args, **kwargs)
 
 
+_STEREO_SUBSET_MAX = 32768   # mm_stereo_product_loss_subset: batch positions per call
+
+
 class StereographicProductEmbedding(torch.nn.Module):
     """n points on a product of constant-curvature factors with learnable curvatures — the counterpart of the reference's
     products/embedding.py:8-60 on `graphembed.manifolds.Stereographic`: `ds` lists the factors' dimensions, `kwargs` go to
@@ -528,6 +531,7 @@ class StereographicProductEmbedding(torch.nn.Module):
         self.r_max = r_max
         self.n_components = len(self.ds)
         self.manifolds = torch.nn.ModuleList([Stereographic(d, **kwargs) for d in self.ds])
+        self._subset_ws = {}   # batch-sized workspaces of the in-kernel minibatch route (a captured step refers to them)
         # relies on default placement, as the reference does: move with `.to(device)`
         self.xs = torch.nn.ParameterList([ManifoldParameter(data=man.rand(n), manifold=man) for man in self.manifolds])
 
@@ -575,12 +579,27 @@ class StereographicProductEmbedding(torch.nn.Module):
             return product_pdist(self.manifolds, xs)
         return sum(man.pdist(x, squared=True) for man, x in zip(self.manifolds, xs))
 
-    def fused_objective(self, objective_fn, gdists, i=None, rows=None, validated=False, **kwargs):
+    def fused_objective(self, objective_fn, gdists, i=None, rows=None, dense=None, validated=False, **kwargs):
         """`objective_fn(gdists, self.compute_dists(i), **kwargs)` and its gradients by ONE pair pass over all factors
         (mm_stereo_product_loss), or None when there is no such kernel: a loss without `fused_spec` (SNE), CPU tensors, more
-        than 8 factors, `pair_kernel = False`.  A node minibatch `i` gathers its rows with `take_rows`: gradients outside the
-        batch are exactly zero.  `rows` selects the pair-list slice of one shard."""
-        if not hasattr(objective_fn, 'fused_spec') or gdists is None or not self._fused():
+        than 8 factors, `pair_kernel = False`.  A node minibatch `i` with the dataset's dense target matrix `dense` (a
+        contiguous [n, n] matrix of the points' dtype on their device; `gdists` may then be None) stays inside the pair kernel
+        (mm_stereo_product_loss_subset): it reads rows `i` of the full tables and the targets dense[i[a], i[b]] itself and
+        writes full-size gradients - the indices must be distinct, host-side ones are checked here unless `validated`.
+        Without `dense` the batch gathers its rows with `take_rows`.  Either way gradients outside the batch are exactly
+        zero.  `rows` selects the pair-list slice of one shard."""
+        if not hasattr(objective_fn, 'fused_spec') or not self._fused():
+            return None
+        in_kernel = (i is not None and dense is not None and dense.is_cuda and dense.device == self.xs[0].device
+                     and dense.dtype == self.xs[0].dtype and dense.is_contiguous() and tuple(dense.shape) == (self.n, self.n))
+        if in_kernel and not validated:
+            i, distinct = prepare_indices(i, self.n)
+            in_kernel, validated = distinct, True
+        if in_kernel and 1 <= i.numel() <= _STEREO_SUBSET_MAX:
+            from graphembed.manifolds.stereographic import product_loss_subset
+            return product_loss_subset(self.manifolds, list(self.xs), i, dense, objective_fn.fused_spec(**kwargs), self._subset_ws,
+                                       rows=rows)
+        if gdists is None:
             return None
         from graphembed.manifolds.stereographic import product_loss
         if i is not None and not validated:

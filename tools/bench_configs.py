@@ -155,6 +155,61 @@ def stereo_step_case(ds, n, dtype, graph=False, fused=False, quotient=False):
     return {'n': n, 'pairs': P, 'dtype': str(dtype).split('.')[-1], 'step_us': t, 'pairs_per_s': P / (t * 1e-6)}
 
 
+def stereo_minibatch_case(ds, n, bs, dtype, graph=False, in_kernel=True):
+    """node-minibatch training step of a product of constant-curvature factors as the reference's product grid runs it
+    (experiments/products/run_prod_grid.py: RiemannianAdam, the points exact, the curvatures a group of their own; stabilize):
+    objective over the batch + backward + Adam + stabilize.  `in_kernel`: the index vector inside the pair kernel
+    (mm_stereo_product_loss_subset) and one mm_stereo_radam_step per factor; otherwise the route before them - the dataset's
+    target gather, `take_rows`, mm_stereo_product_loss, scatter-add backward, and Adam composed from the class's maps"""
+    from graphembed.data import GraphDataset
+    from graphembed.modules import BatchedObjective, StereographicProductEmbedding
+    torch.manual_seed(0)
+    emb = StereographicProductEmbedding(n, ds).to(device='cuda', dtype=dtype)
+    data = GraphDataset(torch.rand(n * (n - 1) // 2, dtype=dtype, device='cuda') * 0.99 + 0.01)
+    if not in_kernel:
+        class Gathered:   # the same targets without the dense matrix on offer
+            __getitem__ = staticmethod(data.__getitem__)
+        data = Gathered()
+        for man in emb.manifolds:
+            man.radam_step = None   # RiemannianAdam then composes the update from egrad2rgrad / norm / exp / transp
+    obj = BatchedObjective(StressLoss(), data, emb)
+    opt = RiemannianAdam([dict(params=list(emb.xs), lr=0.05, exact=True), dict(params=list(emb.curvature_params), lr=0.05)])
+    perm = torch.randperm(n, device='cuda')
+    idx = perm[:bs].clone()
+    state = {'i': 0}
+
+    def step():
+        opt.zero_grad(set_to_none=True)
+        loss = obj(idx)
+        loss.backward(unit_seed(loss))
+        opt.step()
+        emb.stabilize()
+
+    def advance():
+        i = state['i']
+        idx.copy_(perm[i:i + bs])
+        state['i'] = (i + bs) % max(n - bs, 1)
+    if graph:
+        side = torch.cuda.Stream()
+        with torch.cuda.stream(side):
+            for _ in range(3):
+                step()
+        torch.cuda.current_stream().wait_stream(side)
+        gr = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(gr):
+            step()
+        run = gr.replay
+    else:
+        run = step
+
+    def timed():
+        advance()
+        run()
+    t = timeit(timed, iters=50)
+    P = bs * (bs - 1) // 2
+    return {'n': n, 'pairs': P, 'dtype': str(dtype).split('.')[-1], 'step_us': t, 'pairs_per_s': P / (t * 1e-6)}
+
+
 CASES = {
     'c1_tree40_euclidean10_f64': lambda: pdist_case(M.Euclidean(10), 40, torch.float64),
     'c2_facebook_lorentz11_f32_gram': lambda: pdist_case(M.Lorentz(11), 4039, torch.float32),
@@ -255,6 +310,16 @@ CASES = {
     'stereo5x5_quotient_step_n1025_f32': lambda: stereo_step_case([5, 5], 1025, torch.float32, quotient=True),
     'stereo5x5_quotient_step_n1025_f32_fused': lambda: stereo_step_case([5, 5], 1025, torch.float32, fused=True, quotient=True),
     'lorentz5x5_step_n1025_f32': lambda: step_case([M.Lorentz(5), M.Lorentz(5)], 1025, torch.float32),
+    # node minibatches with RiemannianAdam, the regime of the reference's product grid: the index vector inside the pair kernel and
+    # the fused Adam step, and their twins on the route before them (`_gathered`: take_rows + Adam composed from the maps)
+    'stereo5x5_minibatch512_radam_step_n4039_f32': lambda: stereo_minibatch_case([5, 5], 4039, 512, torch.float32),
+    'stereo5x5_minibatch512_radam_step_n4039_f32_graph': lambda: stereo_minibatch_case([5, 5], 4039, 512, torch.float32, graph=True),
+    'stereo5x5_minibatch512_radam_step_n4039_f32_gathered': lambda: stereo_minibatch_case([5, 5], 4039, 512, torch.float32, in_kernel=False),
+    'stereo5x5_minibatch512_radam_step_n4039_f32_gathered_graph': lambda: stereo_minibatch_case([5, 5], 4039, 512, torch.float32, graph=True, in_kernel=False),
+    'stereo2x8_minibatch4096_radam_step_n8192_f32': lambda: stereo_minibatch_case([2] * 8, 8192, 4096, torch.float32),
+    'stereo2x8_minibatch4096_radam_step_n8192_f32_graph': lambda: stereo_minibatch_case([2] * 8, 8192, 4096, torch.float32, graph=True),
+    'stereo2x8_minibatch4096_radam_step_n8192_f32_gathered': lambda: stereo_minibatch_case([2] * 8, 8192, 4096, torch.float32, in_kernel=False),
+    'stereo2x8_minibatch4096_radam_step_n8192_f32_gathered_graph': lambda: stereo_minibatch_case([2] * 8, 8192, 4096, torch.float32, graph=True, in_kernel=False),
     'c4_csphd_sne_incl_step_f32_graph': lambda: step_case([M.Lorentz(6), M.Sphere(6), M.SymmetricPositiveDefinite(2)], 1025, torch.float32, sne='incl', graph=True),
 }
 
