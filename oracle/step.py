@@ -119,10 +119,10 @@ def _d2_and_grad(factor, x, lo, hi, g=None):
     return exact.vec_pairs(kind, x, lo, hi) if g is None else exact.vec_pairs_grad(kind, x, lo, hi, g)
 
 
-def pair_distances(factors, xs, idx=None):
+def pair_distances(factors, xs, idx=None, pairs=None):
     """Squared distances of every factor over the step's pair list (the expensive half of `objective`)."""
     xs = [np.ascontiguousarray(x, dtype=np.float64) for x in xs]
-    i, j = pair_list(xs[0].shape[0], idx)
+    i, j = pair_list(xs[0].shape[0], idx) if pairs is None else _explicit_pairs(pairs)
     lo, hi = np.minimum(i, j), np.maximum(i, j)
     return [_d2_and_grad(f, x, lo, hi) for f, x in zip(factors, xs)]
 
@@ -142,12 +142,20 @@ def kink_distance(loss, gd, md):
     return out
 
 
-def objective(factors, xs, scales, loss, target=None, dense=None, idx=None, d2=None):
+def _explicit_pairs(pairs):
+    i, j = (np.ascontiguousarray(p, dtype=np.int64) for p in pairs)
+    assert i.shape == j.shape and i.ndim == 1, (i.shape, j.shape)
+    return i, j
+
+
+def objective(factors, xs, scales, loss, target=None, dense=None, idx=None, d2=None, pairs=None):
     """Loss and the Euclidean gradients of every factor's points (dense: zero rows outside a minibatch; SPD: the symmetric
-    part) and raw scales.  `d2`: the result of `pair_distances` on the same points, when the caller has it already."""
+    part) and raw scales.  `d2`: the result of `pair_distances` on the same points, when the caller has it already.
+    `pairs`: an explicit (i, j) list of node pairs in place of `pair_list(n, idx)` — a row shard of the pair vector, say;
+    `target` then holds one entry per listed pair (points no listed pair touches get zero gradients)."""
     xs = [np.ascontiguousarray(x, dtype=np.float64) for x in xs]
     n = xs[0].shape[0]
-    i, j = pair_list(n, idx)
+    i, j = pair_list(n, idx) if pairs is None else _explicit_pairs(pairs)
     gd = pair_targets(target, dense, i, j)
     lo, hi = np.minimum(i, j), np.maximum(i, j)
     if d2 is None:

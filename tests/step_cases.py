@@ -84,6 +84,11 @@ CASES = [
     case('a-csphd-n257-momentum-f32', 'fused', CSPHD, 257, 'f32', 'momentum', 'rsgd', 'all'),
     case('a-four-n131-adam_nc-f32', 'fused', FOUR, 131, 'f32', 'adam_nc', 'momentum', 'none', loss='quotient'),
     case('a-four-n2-rsgd_retr-f64', 'fused', FOUR, 2, 'f64', 'rsgd_retr', 'rsgd_noclip', None),
+    # product_step_kernel<T, SD> without an SPD factor (SD = 0: two and three vector factors), and one vector factor + SPD
+    case('a-l4e3-n131-rsgd-f32', 'fused', [('lorentz', 4), ('euclidean', 3)], 131, 'f32', 'rsgd', 'rsgd', 'median'),
+    case('a-s5l8e7-n65-adam-f64', 'fused', [('sphere', 5), ('lorentz', 8), ('euclidean', 7)], 65, 'f64', 'adam', 'adam', 'median',
+         loss='quotient'),
+    case('a-e6spd2-n129-momentum-f32', 'fused', [('euclidean', 6), ('spd', 2)], 129, 'f32', 'momentum', 'rsgd', 'all'),
     # the BASELINE sizes (one per family: the oracle costs CPU seconds per step there)
     case('a-spd3-n5000-rsgd-f32', 'fused', [('spd', 3)], 5000, 'f32', 'rsgd', 'rsgd', 'median', big=True),
     case('a-spd4-n2274-rsgd-f32', 'fused', [('spd', 4)], 2274, 'f32', 'rsgd', 'rsgd', 'median', loss='quotient', big=True),

@@ -47,7 +47,9 @@ def kernels(lib=LIB):
         mangled = [r['name'] for r in rows if 'name' in r]
         dem = subprocess.run(['c++filt'], input='\n'.join(mangled), capture_output=True, text=True).stdout.splitlines()
         for r, nm in zip([r for r in rows if 'name' in r], dem):
-            nm = re.sub(r'^void ', '', nm).split('(')[0].replace('mm::', '').replace('(anonymous namespace)::', '')
+            # (the anonymous namespace goes BEFORE the cut at the argument list: its '(' used to end the name at 'mm::', and
+            # every kernel of an anonymous namespace — product_sym_kernel among them — fell into one nameless entry)
+            nm = re.sub(r'^void ', '', nm).replace('(anonymous namespace)::', '').split('(')[0].replace('mm::', '')
             out[nm] = dict(vgpr=r.get('vgpr_count', 0), agpr=r.get('agpr', 0), sgpr=r.get('sgpr_count', 0),
                            vgpr_spill=r.get('vgpr_spill_count', 0), sgpr_spill=r.get('sgpr_spill_count', 0),
                            scratch=r.get('private_segment_fixed_size', 0), lds=r.get('group_segment_fixed_size', r.get('lds', 0)))
