@@ -388,6 +388,24 @@ int mm_grass_pdist_loss(int dtype, int loss_kind, const void* x, const void* tar
                         int64_t n, int N, int p, int64_t row_begin, int64_t row_end, double alpha, double eps,
                         int terms, const double* loss_params, void* loss_out, void* grad_x, void* ws,
                         mm_stream_t stream);
+/* mm_grass_pdist_loss for a NODE MINIBATCH, the counterpart of mm_spd_pdist_loss_subset / mm_vec_pdist_loss_subset (the header
+ * comment there applies word for word): x is the FULL table [n_total, N, p]; the points of the step are its rows idx[0..bs)
+ * (device int64, DISTINCT; the kernel reads the low 32 bits and clamps the node id into [0, n_total)); the target of batch pair
+ * (a, b), a < b, is dense[idx[a]][idx[b]] — exactly that element of the contiguous n_total x n_total matrix, no symmetry
+ * assumed; row_begin / row_end shard the pair list of the BATCH (positions 0 .. bs); grad_x [n_total, N, p] is OVERWRITTEN:
+ * rows idx[.] with this shard's partial gradient, every other row with +0; loss_out = { loss, d loss / d scale_raw }.
+ * ws: mm_grass_pdist_loss_ws_bytes(dtype, n_total, N, p) — sized by the table, not by the batch, so one buffer serves every
+ * batch of an epoch and a captured step; the call clears it itself.  A step is a memset, the pair kernel (the accumulators are
+ * addressed by node) and the finalize launch over n_total; nothing allocates and nothing synchronises.  bs = 0, bs = 1 or an
+ * empty row range writes a zero gradient and {0, 0} without a pair kernel.  Limits as mm_grass_pdist_loss (N <= 9, p <= 4,
+ * p <= N, n_total <= 2^30, bs <= n_total, the tile count in one grid dimension), errors before anything touches the GPU.
+ * mm_grass_pdist_loss_subset_form: 1 when (dtype, N, p) is built (every one is today); MM_ERR_UNSUPPORTED for an instantiation
+ * left out because it would need scratch inside the row loop (the entry point then returns the same); MM_ERR_ARG as above. */
+int mm_grass_pdist_loss_subset_form(int dtype, int N, int p);
+int mm_grass_pdist_loss_subset(int dtype, int loss_kind, const void* x, const void* dense, const void* scale_raw,
+                               int64_t n_total, int N, int p, const int64_t* idx, int64_t bs, int64_t row_begin,
+                               int64_t row_end, double alpha, double eps, int terms, const double* loss_params,
+                               void* loss_out, void* grad_x, void* ws, mm_stream_t stream);
 /* Fused RiemannianSGD update of Grassmann / Stiefel points (rsgd.py:40-82), one launch: rgrad = proju(x, egrad), clipped by
  * max_grad_norm / sqrt(max(||rgrad||_F^2, 1e-8)) capped at 1 when max_grad_norm > 0, x_new = step(x, -lr * rgrad) with
  * step = retr_op (MM_MAT_RETR_SVD or MM_MAT_RETR_QR) or, with `exact`, MM_MAT_EXP (Grassmann only: Stiefel returns
@@ -399,6 +417,20 @@ int mm_mat_rsgd_step(int dtype, int kind, int retr_op, const void* x, const void
 int mm_mat_rsgd_momentum_step(int dtype, int kind, int retr_op, const void* x, const void* egrad,
                               void* momentum_buffer, int64_t cnt, int N, int p, double lr, double momentum,
                               double dampening, double max_grad_norm, int exact, void* x_new, mm_stream_t stream);
+/* Fused RiemannianAdam update of Grassmann / Stiefel points (radam.py:62-98), one launch, one thread per point, in the
+ * reference's order: rgrad = proju(x, egrad); gn^2 = max(||rgrad||_F^2, 1e-8), taken BEFORE the clip by min(max_grad_norm / gn,
+ * 1) (max_grad_norm > 0); exp_avg = beta1 exp_avg + (1 - beta1) rgrad; exp_avg_sq = beta2 exp_avg_sq + (1 - beta2) gn^2 — ONE
+ * scalar per point, stored broadcast over it, as mm_spd_radam_step does; x_new = step(x, -alpha exp_avg / (sqrt(exp_avg_sq) +
+ * eps)) with alpha = lr sqrt(1 - beta2^t) / (1 - beta1^t), beta2 = 1 - 1/t when `nc`, and step = retr_op or, with `exact`,
+ * MM_MAT_EXP (Grassmann only: Stiefel returns MM_ERR_UNSUPPORTED); exp_avg is then transported to x_new (proju(x_new, .),
+ * base.py:65-66) IN PLACE.  `step` (device fp64 scalar t >= 1) is advanced by the kernel and `ticket` (device counter, zero
+ * between launches) re-armed, as in mm_vec_radam_step: a captured graph keeps counting.  1 - beta is formed in fp64 from the
+ * fp64 arguments.  Grassmann at N = p (a single point, no tangent directions): `exact` moves with retr_op, which keeps the frame
+ * orthonormal where exp would carry normalised rounding noise into x_new^T x_new.  All tensors are [cnt,N,p]; x_new may equal x.  A point with a zero gradient and a zero first moment comes
+ * out as itself (exp: bit for bit; the retractions: polar(x) / Q(x), x to rounding). */
+int mm_mat_radam_step(int dtype, int kind, int retr_op, const void* x, const void* egrad, void* exp_avg, void* exp_avg_sq,
+                      double* step, unsigned* ticket, int64_t cnt, int N, int p, double lr, double beta1, double beta2,
+                      int nc, double eps, double max_grad_norm, int exact, void* x_new, mm_stream_t stream);
 
 /* ---- stochastic-neighbour KL objective ---------------------------------------- */
 /* The reference's KLDiveregenceLoss('sne', inclusive) (objectives.py:48-76, inference/stochastic_neighbors.py:8-24) on

@@ -19,134 +19,20 @@
 
 #include <climits>
 
-#include "../../include/mm_manifolds.h"
-#include "loss.hpp"
-#include "mat_common.hpp"
-#include "smallmat.hpp"
+#include "grass_loss.hpp"
 
 namespace mm {
 namespace mat {
 
-constexpr int kLossTI = 16;    // rows per tile (one wavefront per workgroup)
-
-// Which form an instantiation takes (reported by mm_grass_pdist_loss_form): 1 = symmetric; 0 would be the ordered scheme.
-template <typename T, int NP, int P> constexpr int loss_form() { return 1; }
-// matrix rows per transposing reduction (form 1)
-template <typename T, int NP> constexpr int group_rows() { return sizeof(T) == 4 ? NP : 1; }
-
-template <typename T, int NP, int P, int LOSS>
-__global__ __launch_bounds__(64) void grass_loss_sym_kernel(const T* __restrict__ x, const T* __restrict__ target, int n, int N,
-                                                            int row_begin, int row_end, int gx, int jb0, LossArgs<T> la,
-                                                            T* __restrict__ acc /* [N*P][n] */) {
-  using Nm = Num<T>;
-  constexpr int TI = kLossTI, GR = group_rows<T, NP>(), GV = GR * P;
-  static_assert(NP % GR == 0, "whole groups");
-  __shared__ T red[TI][NP * P];
-  const int lane = threadIdx.x;
-  const int by = int(blockIdx.x) / gx, bx = int(blockIdx.x) - by * gx;
-  const int i0 = row_begin + by * TI, i1 = min(i0 + TI, row_end);
-  const int jbase = (jb0 + bx) * 64;   // (< n: gx = ceil(n / 64) - jb0)
-  if (jbase + 63 <= i0) return;        // no column right of the tile's first row, so of none of its rows
-  loss_resolve<T, LOSS>(la);
-  const T sp = softplus_of(la.scale_raw);
-  const int j = jbase + lane;
-  const bool jin = j < n;
-  bool writer;
-  const int slot = reduce_slot<GV>(lane, writer);
-  T xj[NP][P], a[NP][P];
-  load<T, NP, P>(x + size_t(jin ? j : 0) * N * P, N, xj);
-#pragma unroll
-  for (int r = 0; r < NP; ++r)
-#pragma unroll
-    for (int c = 0; c < P; ++c) a[r][c] = T(0);
-  T loss_acc = T(0), ds_acc = T(0);
-  const int64_t base = moff(n, row_begin);
-  const int ilast = min(i1, jbase + 63);   // rows from here on have no column in this block
-  for (int i = i0; i < ilast; ++i) {
-    T xi[NP][P], gm[P][P], dg[P][P];
-    load<T, NP, P>(x + size_t(i) * N * P, N, xi);  // wave-uniform -> scalar loads
-    const bool valid = jin && j > i;
-    T tg = T(1);
-    if (valid) tg = target[moff(n, i) - base + (j - i - 1)];
-    gram<T, NP, P>(xi, xj, gm);  // x_i^T x_j ; d/dx_j = x_i dG, d/dx_i = x_j dG^T
-    const T v = grass_pair<T, P, true>(gm, dg);
-    T dldm;
-    const T l = loss_term<T, LOSS>(sp * v, tg, la, dldm);
-    loss_acc += valid ? l : T(0);
-    ds_acc += valid ? dldm * v : T(0);
-    const T w = valid ? dldm * sp : T(0);
-#pragma unroll
-    for (int r = 0; r < NP; ++r)
-#pragma unroll
-      for (int c = 0; c < P; ++c) {
-        T s = T(0);
-#pragma unroll
-        for (int k = 0; k < P; ++k) s = Nm::fma(xi[r][k], dg[k][c], s);
-        a[r][c] = Nm::fma(w, s, a[r][c]);
-      }
-#pragma unroll
-    for (int g = 0; g < NP / GR; ++g) {
-      T rs[GV];
-#pragma unroll
-      for (int rr = 0; rr < GR; ++rr)
-#pragma unroll
-        for (int c = 0; c < P; ++c) {
-          T s = T(0);
-#pragma unroll
-          for (int k = 0; k < P; ++k) s = Nm::fma(xj[g * GR + rr][k], dg[c][k], s);
-          rs[rr * P + c] = w * s;
-        }
-      const T tot = wave_reduce_transposed<GV, T>(rs, lane);
-      if (writer) red[i - i0][g * GV + slot] = tot;
-    }
-  }
-  __builtin_amdgcn_wave_barrier();
-  {
-    const int np = N * P, cnt = (ilast - i0) * np;   // (rows r >= N of the padded point are not flushed)
-    for (int t = lane; t < cnt; t += 64) {
-      const int il = t / np, k = t - il * np;
-      atomic_add(&acc[size_t(k) * n + (i0 + il)], red[il][k]);
-    }
-  }
-  if (jin) {
-#pragma unroll
-    for (int r = 0; r < NP; ++r)
-#pragma unroll
-      for (int c = 0; c < P; ++c)
-        if (r < N) atomic_add(&acc[size_t(r * P + c) * n + j], a[r][c]);
-  }
-  const T ls = wave_sum(loss_acc), dd = wave_sum(ds_acc);
-  if (lane == 0) {
-    const int s = blockIdx.x & (kLossSlots - 1);
-    atomic_add(&la.slots[s], ls);
-    atomic_add(&la.slots[kLossSlots + s], dd);
-  }
-}
-
-// grad [n][np] from the transposed accumulators; the first wavefront of block 0 closes the loss record
-template <typename T>
-__global__ __launch_bounds__(128) void grass_loss_finalize_kernel(const T* __restrict__ acc, int n, int np, T* __restrict__ grad,
-                                                                  T* __restrict__ slots, const T* __restrict__ scale_raw,
-                                                                  T* __restrict__ loss_out) {
-  const int j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j < n)
-    for (int k = 0; k < np; ++k) grad[size_t(j) * np + k] = acc[size_t(k) * n + j];
-  if (blockIdx.x == 0 && threadIdx.x < 64) loss_finalize<T>(slots, scale_raw, loss_out);
-}
-
-inline size_t loss_acc_bytes(int dtype, int64_t n, int N, int p) {
-  const size_t b = (dtype == MM_F64 ? 8 : 4) * size_t(n) * size_t(N) * size_t(p);
-  return (b + 255) & ~size_t(255);
-}
-
+// (the pair kernel lives in grass_loss.hpp, shared with the node-minibatch instantiations of grass_loss_subset.hip)
 template <typename T, int NP, int P, int LOSS>
 int launch_loss(const T* x, const T* target, int64_t n, int N, int64_t rb, int64_t re, LossArgs<T> la, T* acc, hipStream_t st) {
   static_assert(loss_form<T, NP, P>() == 1, "only the symmetric form is built");
   const int jb0 = int((rb + 1) / 64);
   const int64_t gx = (n + 63) / 64 - jb0, gy = (re - rb + kLossTI - 1) / kLossTI;
   if (gx <= 0 || gy <= 0) return MM_OK;
-  grass_loss_sym_kernel<T, NP, P, LOSS><<<dim3(unsigned(gx * gy)), dim3(64), 0, st>>>(x, target, int(n), N, int(rb), int(re),
-                                                                                    int(gx), jb0, la, acc);
+  grass_loss_sym_kernel<T, NP, P, LOSS, false><<<dim3(unsigned(gx * gy)), dim3(64), 0, st>>>(x, target, int(n), N, int(rb), int(re),
+                                                                                           int(gx), jb0, la, acc, int(n), nullptr);
   MMM_CHECK();
   return MM_OK;
 }

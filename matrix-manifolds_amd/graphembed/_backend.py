@@ -119,6 +119,9 @@ SIGNATURES = {
     'mm_grass_pdist_loss_ws_bytes': (_sz, [_i, _i64, _i, _i]),
     'mm_grass_pdist_loss_form': (_i, [_i, _i, _i]),
     'mm_grass_pdist_loss': (_i, [_i, _i, _vp, _vp, _vp, _i64, _i, _i, _i64, _i64, _dbl, _dbl, _i, _vp, _vp, _vp, _vp, _vp]),
+    'mm_grass_pdist_loss_subset_form': (_i, [_i, _i, _i]),
+    'mm_grass_pdist_loss_subset': (_i, [_i, _i, _vp, _vp, _vp, _i64, _i, _i, _vp, _i64, _i64, _i64, _dbl, _dbl, _i, _vp, _vp, _vp,
+                                        _vp, _vp]),
     'mm_sne_kl_ws_bytes': (_sz, [_i, _i64]),
     'mm_sne_kl_loss': (_i, [_i, _i, _vp, _vp, _i64, _dbl, _vp, _vp, _vp, _vp]),
     'mm_stereo_pdist_ws_bytes': (_sz, [_i, _i64, _i]),
@@ -136,6 +139,8 @@ SIGNATURES = {
     'mm_stereo_product_loss_subset': (_i, [_i, _i, _vp, _i, _vp, _i64, _vp, _i64, _i64, _i64, _dbl, _dbl, _i, _vp, _vp, _vp, _vp]),
     'mm_mat_rsgd_step': (_i, [_i, _i, _i, _vp, _vp, _i64, _i, _i, _dbl, _dbl, _i, _vp, _vp]),
     'mm_mat_rsgd_momentum_step': (_i, [_i, _i, _i, _vp, _vp, _vp, _i64, _i, _i, _dbl, _dbl, _dbl, _dbl, _i, _vp, _vp]),
+    'mm_mat_radam_step': (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _dbl, _dbl, _dbl, _i, _dbl, _dbl, _i, _vp,
+                               _vp]),
 }
 GRASSMANN, STIEFEL = 0, 1
 SNE_INCLUSIVE, SNE_EXCLUSIVE = 0, 1  # MM_SNE_*

@@ -107,6 +107,47 @@ class _GrassPdistLoss(torch.autograd.Function):
         return gx, gs, None, None, None, None, None, None
 
 
+class _GrassSubsetLoss(torch.autograd.Function):
+    """Objective and gradients of a node minibatch inside the Grassmann pair kernel (mm_grass_pdist_loss_subset): the
+    index vector addresses the rows of the full table, the targets dense[idx[a]][idx[b]] and the gradient rows — no
+    gather, no scatter-add, no zero fill (the sibling of graphembed.modules._SingleSubsetLoss).  The workspace is sized
+    by the table and kept in `cache` for the embedding's lifetime: a captured graph of the step refers to it."""
+
+    @staticmethod
+    def forward(ctx, spec, rows, N, p, cache, idx, dense, x, scale):
+        B.require_gpu(x, dense)
+        lib = B.lib()
+        lkind, alpha, eps, terms = spec[:4]
+        dyn = spec[4] if len(spec) > 4 else None
+        dtype, dev = x.dtype, x.device
+        n_total, bs = x.shape[0], idx.numel()
+        rb, re = (0, bs) if rows is None else rows
+        dt = B.dtype_code(x)
+        if dense.dtype != dtype or not dense.is_contiguous() or dense.shape != (n_total, n_total):
+            raise ValueError('dense targets must be a contiguous [n, n] matrix of the embedding\'s dtype')
+        with B.on_device(dev):
+            xc = x.detach().contiguous()
+            sc = scale.detach().to(dtype).reshape(1).contiguous()
+            ic = idx.to(device=dev, dtype=torch.int64).contiguous()
+            out = torch.empty(2, dtype=dtype, device=dev)
+            grad = torch.empty_like(xc)
+            key = ('grass', dtype, dev, n_total, N, p)
+            ws = cache.get(key) if cache is not None else None
+            if ws is None:
+                ws = torch.empty(lib.raw('mm_grass_pdist_loss_ws_bytes')(dt, n_total, N, p), dtype=torch.uint8, device=dev)
+                if cache is not None:
+                    cache[key] = ws
+            lib.call('mm_grass_pdist_loss_subset', dt, B.LOSS_STRESS if lkind == 'stress' else B.LOSS_QUOTIENT, B.ptr(xc),
+                     B.ptr(dense), B.ptr(sc), n_total, N, p, B.ptr(ic), bs, rb, re, alpha, eps, terms, B.dyn_ptr(dyn, x),
+                     B.ptr(out), B.ptr(grad), B.ptr(ws), B.stream_of(x))
+        ctx.grads = [grad.reshape(x.shape), out[1].reshape(scale.shape).to(scale.dtype)]
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, up):
+        return (None, None, None, None, None, None, None) + tuple(B.take_grads(ctx, up, 'grads'))
+
+
 class _MatrixManifold(Manifold):
     _kind = None
 
@@ -212,6 +253,27 @@ class _MatrixManifold(Manifold):
                          int(bool(exact)), B.ptr(out), B.stream_of(xc))
         return x if inplace else out.reshape(x.shape)
 
+    def radam_step(self, x, egrad, exp_avg, exp_avg_sq, step, ticket, *, lr, betas, nc, eps, max_grad_norm=None,
+                   exact=False, inplace=False):
+        """Fused RiemannianAdam update (optim/radam.py:62-98) in one launch (mm_mat_radam_step), with this instance's
+        retraction (or `exp` when `exact`): moments updated in place, `step` (device fp64 scalar) advanced by the
+        kernel; returns the new points (`x` itself when `inplace`), or None when the tensors are not eligible (CPU
+        tensors, non-contiguous or mistyped moments, Stiefel with `exact`)."""
+        if not (self._step_eligible(x, egrad, exact, exp_avg) and self._step_eligible(x, egrad, exact, exp_avg_sq)):
+            return None
+        xd = x.detach()
+        inplace = inplace and xd.is_contiguous()
+        xc = xd.reshape(-1, self.n, self.p).contiguous()
+        gc = egrad.detach().reshape(-1, self.n, self.p).contiguous()
+        with B.on_device(xc.device):
+            out = xc if inplace else torch.empty_like(xc)
+            B.lib().call('mm_mat_radam_step', B.dtype_code(xc), self._kind, self._retr_op, B.ptr(xc), B.ptr(gc),
+                         B.ptr(exp_avg), B.ptr(exp_avg_sq), B.ptr(step), B.ptr(ticket), xc.shape[0], self.n, self.p,
+                         float(lr), float(betas[0]), float(betas[1] if betas[1] is not None else 0.0), int(bool(nc)),
+                         float(eps), -1.0 if max_grad_norm is None else float(max_grad_norm), int(bool(exact)),
+                         B.ptr(out), B.stream_of(xc))
+        return x if inplace else out.reshape(x.shape)
+
     def rand(self, *shape, out=None, ir=1e-2):
         x = self.zero(*shape, out=out)
         with torch.no_grad():
@@ -270,6 +332,21 @@ class Grassmann(_MatrixManifold):
         assert x.ndim == 3
         rb, re = (0, x.shape[0]) if rows is None else rows
         return _GrassPdistLoss.apply(x, scale, target, self.n, self.p, spec, rb, re)
+
+    def subset_form(self, x):
+        """Can mm_grass_pdist_loss_subset take a node minibatch of the table `x`?  (GPU, fp32 / fp64, [n, N, p], and an
+        instantiation the library has built.)"""
+        if not (x.is_cuda and x.dtype in (torch.float32, torch.float64) and x.ndim == 3
+                and tuple(x.shape[-2:]) == (self.n, self.p)):
+            return False
+        return B.lib().raw('mm_grass_pdist_loss_subset_form')(B.dtype_code(x), self.n, self.p) == 1
+
+    def pdist_loss_subset(self, x, scale, idx, dense, spec, rows=None, cache=None):
+        """`pdist_loss` for the node minibatch `idx` of the full table `x` with the targets dense[idx[a], idx[b]], inside
+        the pair kernel; None when the tensors are not eligible (the caller then gathers)."""
+        if not (self.subset_form(x) and dense.is_cuda):
+            return None
+        return _GrassSubsetLoss.apply(spec, rows, self.n, self.p, cache, idx, dense, x, scale)
 
     def __str__(self):
         return 'Grassmann manifold of {}x{} matrices'.format(self.n, self.p)

@@ -454,6 +454,12 @@ class ManifoldEmbedding(torch.nn.Module):
                 factor = _single_subset_factor(self.manifolds[0])
                 if factor is not None:
                     return _SingleSubsetLoss.apply(spec, rows, self.manifolds[0], factor, self._pair_ws, i, dense, pts[0], scales[0])
+                # Grassmann: its own pair kernel with the index vector (mm_grass_pdist_loss_subset)
+                subset = getattr(self.manifolds[0], 'pdist_loss_subset', None)
+                if subset is not None:
+                    loss = subset(pts[0], scales[0], i, dense, spec, rows=rows, cache=self._pair_ws)
+                    if loss is not None:
+                        return loss
         if self.n_components == 1 and getattr(self.manifolds[0], 'pdist_loss', None) is not None:
             if gdists is None:
                 return None

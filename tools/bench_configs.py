@@ -210,6 +210,64 @@ def stereo_minibatch_case(ds, n, bs, dtype, graph=False, in_kernel=True):
     return {'n': n, 'pairs': P, 'dtype': str(dtype).split('.')[-1], 'step_us': t, 'pairs_per_s': P / (t * 1e-6)}
 
 
+def grass_minibatch_case(N, p, n, bs, dtype, graph=False, in_kernel=True):
+    """node-minibatch training step of a Grassmann embedding as the reference's grid runs it (experiments/run_grid.py:24-36,
+    123-134: RiemannianAdam(lr=0.01, exact=True, max_grad_norm=100), batch_size=512): objective over the batch + backward +
+    Adam on the points and on the scale.  `in_kernel`: the index vector inside the pair kernel (mm_grass_pdist_loss_subset) and
+    one mm_mat_radam_step; otherwise the route before them - the dataset's target gather, `take_rows`, mm_grass_pdist_loss,
+    scatter-add backward, and Adam composed from egrad2rgrad / norm / exp / transp"""
+    from graphembed.data import GraphDataset
+    from graphembed.modules import BatchedObjective
+    torch.manual_seed(0)
+    torch.set_default_dtype(dtype)
+    try:
+        with torch.device('cuda'):
+            emb = ManifoldEmbedding(n, [M.Grassmann(N, p)])
+    finally:
+        torch.set_default_dtype(torch.float32)
+    data = GraphDataset(torch.rand(n * (n - 1) // 2, dtype=dtype, device='cuda') * 0.99 + 0.01)
+    if not in_kernel:
+        class Gathered:   # the same targets without the dense matrix on offer
+            __getitem__ = staticmethod(data.__getitem__)
+        data = Gathered()
+        emb.manifolds[0].radam_step = None   # RiemannianAdam then composes the update
+    obj = BatchedObjective(StressLoss(), data, emb)
+    opt = RiemannianAdam([dict(params=list(emb.xs), lr=0.01, exact=True, max_grad_norm=100), dict(params=list(emb.scales), lr=0.01)])
+    perm = torch.randperm(n, device='cuda')
+    idx = perm[:bs].clone()
+    state = {'i': 0}
+
+    def step():
+        opt.zero_grad(set_to_none=True)
+        loss = obj(idx)
+        loss.backward(unit_seed(loss))
+        opt.step()
+
+    def advance():
+        i = state['i']
+        idx.copy_(perm[i:i + bs])
+        state['i'] = (i + bs) % max(n - bs, 1)
+    if graph:
+        side = torch.cuda.Stream()
+        with torch.cuda.stream(side):
+            for _ in range(3):
+                step()
+        torch.cuda.current_stream().wait_stream(side)
+        gr = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(gr):
+            step()
+        run = gr.replay
+    else:
+        run = step
+
+    def timed():
+        advance()
+        run()
+    t = timeit(timed, iters=50)
+    P = bs * (bs - 1) // 2
+    return {'n': n, 'pairs': P, 'dtype': str(dtype).split('.')[-1], 'step_us': t, 'pairs_per_s': P / (t * 1e-6)}
+
+
 CASES = {
     'c1_tree40_euclidean10_f64': lambda: pdist_case(M.Euclidean(10), 40, torch.float64),
     'c2_facebook_lorentz11_f32_gram': lambda: pdist_case(M.Lorentz(11), 4039, torch.float32),
@@ -283,6 +341,15 @@ CASES = {
     'grassmann94_step_n2000_f32': lambda: step_case([M.Grassmann(9, 4)], 2000, torch.float32),
     'grassmann94_step_n2000_f32_fused': lambda: step_case([M.Grassmann(9, 4)], 2000, torch.float32, fused=True),
     'grassmann94_step_n2000_f32_fused_graph': lambda: step_case([M.Grassmann(9, 4)], 2000, torch.float32, fused=True, graph=True),
+    # node minibatches with Adam, the reference grid's recipe; `_gathered`: the route before mm_grass_pdist_loss_subset / mm_mat_radam_step
+    'grassmann52_minibatch512_radam_step_n2000_f32': lambda: grass_minibatch_case(5, 2, 2000, 512, torch.float32),
+    'grassmann52_minibatch512_radam_step_n2000_f32_graph': lambda: grass_minibatch_case(5, 2, 2000, 512, torch.float32, graph=True),
+    'grassmann52_minibatch512_radam_step_n2000_f32_gathered': lambda: grass_minibatch_case(5, 2, 2000, 512, torch.float32, in_kernel=False),
+    'grassmann52_minibatch512_radam_step_n2000_f32_gathered_graph': lambda: grass_minibatch_case(5, 2, 2000, 512, torch.float32, graph=True, in_kernel=False),
+    'grassmann94_minibatch512_radam_step_n2000_f32': lambda: grass_minibatch_case(9, 4, 2000, 512, torch.float32),
+    'grassmann94_minibatch512_radam_step_n2000_f32_graph': lambda: grass_minibatch_case(9, 4, 2000, 512, torch.float32, graph=True),
+    'grassmann94_minibatch512_radam_step_n2000_f32_gathered': lambda: grass_minibatch_case(9, 4, 2000, 512, torch.float32, in_kernel=False),
+    'grassmann94_minibatch512_radam_step_n2000_f32_gathered_graph': lambda: grass_minibatch_case(9, 4, 2000, 512, torch.float32, graph=True, in_kernel=False),
     # stochastic-neighbour KL loss (StochasticNeighborLoss: pdist forward, mm_sne_kl_loss, pdist backward) | its torch-op form
     'c3_spd3_sne_incl_step_n5000_f32': lambda: step_case([M.SymmetricPositiveDefinite(3)], 5000, torch.float32, sne='incl'),
     'c3_spd3_sne_incl_step_n5000_f32_torchops': lambda: step_case([M.SymmetricPositiveDefinite(3)], 5000, torch.float32, sne='incl', native=False),
