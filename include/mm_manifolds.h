@@ -452,6 +452,36 @@ size_t mm_sne_kl_ws_bytes(int dtype, int64_t n);
 int mm_sne_kl_loss(int dtype, int mode, const void* target, const void* m, int64_t n, double alpha,
                    void* grad_out /* may be null */, void* loss_out, void* ws, mm_stream_t stream);
 
+/* ---- spanning-tree KL objective ------------------------------------------------ */
+/* The reference's KLDiveregenceLoss('sste', inclusive) (objectives.py:48-76, inference/stochastic_trees.py) on pair vectors
+ * in this library's order: with w = exp theta, L(theta) the weighted graph Laplacian without the row and column of node 0,
+ * G = L^-1 (zero row and column for node 0) and q(S)_ij = S_ii + S_jj - 2 S_ij,
+ *   A(theta) = log det L(theta),  mu(theta)_ij = w_ij q(G)_ij,  delta = theta_z - theta_x,
+ *   loss = A(theta_z) - A(theta_x) - mu(theta_x) . delta  = KL(trees(theta_x) || trees(theta_z)),
+ *   MM_SST_INCLUSIVE: theta_x = -alpha * target, theta_z = -m;   d loss / d m = mu(theta_x) - mu(theta_z)
+ *   MM_SST_EXCLUSIVE: theta_x = -m, theta_z = -alpha * target;   d loss / d m_ij = mu_ij delta_ij - w_ij q(G M G)_ij, M the
+ *                     reduced Laplacian of the weights w delta, all at theta_x (the gradient of the loss above)
+ *   MM_SST_EXCLUSIVE_REFERENCE: the same loss;                   d loss / d m_ij = mu_ij delta_ij — what the reference
+ *                     returns: its PLogDet.backward forms L^-1 outside the graph, so d G / d theta is dropped.
+ * target, m: [n (n - 1) / 2] squared graph / manifold distances.  loss_out[0] = loss (one value of `dtype`); grad_out, when
+ * not null, is OVERWRITTEN with d loss / d m, one value per pair.  Passes (csrc/sst_loss.hip): both models are shifted by
+ * their largest theta (the loss and the first two gradients do not change when a constant is added to every m), the two
+ * (n - 1) x (n - 1) Laplacians are factored by a blocked Cholesky in `dtype` with log det accumulated in fp64, the inverse
+ * is formed only for a model whose marginals are needed (theta_x always, theta_z for the inclusive gradient), products run on
+ * the matrix cores (exact f32 / f64).  No float atomics and every sum in a fixed order: bitwise reproducible from call to call.
+ * A pivot that is not finite and positive (a disconnected graph, m = +inf on every pair of a node) gives a non-finite loss
+ * and gradient; the call still returns MM_OK and the next call on the same workspace is unaffected.
+ * ws: mm_sst_kl_ws_bytes(dtype, n) bytes = 5 (n - 1)^2 elements (each matrix rounded up to 256 bytes) + 2 x 256 elements +
+ * 8 (2 ceil((n - 1) / 32) + n - 1) bytes, every part rounded up to 256 (0 for an unknown dtype, n < 2 or n above the limit);
+ * it needs no clearing.  Nothing is allocated and nothing synchronises: the call can be captured in a HIP graph.
+ * MM_ERR_ARG for an unknown dtype or mode, n < 0, a null loss_out and, for n >= 2, a null target, m or ws — before anything
+ * touches the GPU.  n < 2: loss_out[0] = 0, nothing else is read or written.  n > 4096 returns MM_ERR_UNSUPPORTED (the fp64
+ * workspace is 0.67 GB at the limit). */
+enum { MM_SST_INCLUSIVE = 0, MM_SST_EXCLUSIVE = 1, MM_SST_EXCLUSIVE_REFERENCE = 2 };
+size_t mm_sst_kl_ws_bytes(int dtype, int64_t n);
+int mm_sst_kl_loss(int dtype, int mode, const void* target, const void* m, int64_t n, double alpha,
+                   void* grad_out /* may be null */, void* loss_out, void* ws, mm_stream_t stream);
+
 /* ---- constant curvature: the kappa-stereographic model ------------------------ */
 /* The reference's `Universal` manifold (manifolds/universal.py, manifolds/impl/math.py): the Poincare ball for c > 0, the
  * stereographic projection of the sphere for c < 0, curvature K = -c, with c a TRAINABLE parameter.  Points are rows of

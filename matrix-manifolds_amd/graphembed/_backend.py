@@ -124,6 +124,8 @@ SIGNATURES = {
                                         _vp, _vp]),
     'mm_sne_kl_ws_bytes': (_sz, [_i, _i64]),
     'mm_sne_kl_loss': (_i, [_i, _i, _vp, _vp, _i64, _dbl, _vp, _vp, _vp, _vp]),
+    'mm_sst_kl_ws_bytes': (_sz, [_i, _i64]),
+    'mm_sst_kl_loss': (_i, [_i, _i, _vp, _vp, _i64, _dbl, _vp, _vp, _vp, _vp]),
     'mm_stereo_pdist_ws_bytes': (_sz, [_i, _i64, _i]),
     'mm_stereo_pdist_fwd': (_i, [_i, _vp, _i64, _i, _i64, _i64, _i, _vp, _i, _dbl, _vp, _vp]),
     'mm_stereo_pdist_bwd': (_i, [_i, _vp, _vp, _i64, _i, _i64, _i64, _i, _vp, _i, _dbl, _vp, _vp, _vp, _vp]),
@@ -144,6 +146,7 @@ SIGNATURES = {
 }
 GRASSMANN, STIEFEL = 0, 1
 SNE_INCLUSIVE, SNE_EXCLUSIVE = 0, 1  # MM_SNE_*
+SST_INCLUSIVE, SST_EXCLUSIVE, SST_EXCLUSIVE_REFERENCE = 0, 1, 2  # MM_SST_*
 MAT_PROJU, MAT_PROJX, MAT_RETR_SVD, MAT_RETR_QR, MAT_EXP, MAT_LOG = range(6)
 VEC_EGRAD2RGRAD, VEC_PROJU, VEC_EXP, VEC_RETR, VEC_PROJX, VEC_TRANSP, VEC_LOG = range(7)
 STEREO_C_FREE, STEREO_C_POSITIVE, STEREO_C_NEGATIVE = range(3)  # MM_STEREO_C_*

@@ -1,8 +1,9 @@
 """Losses on vectors of *squared* distances used by the path's configs —
 counterparts of graphembed/graphembed/objectives.py:16-45 (Stress, Quotient).
 PearsonRLoss runs on the differentiable pdist path.  StochasticNeighborLoss is the reference's
-KLDiveregenceLoss('sne', inclusive) (objectives.py:48-76) on the kernels of csrc/sne_loss.hip; the spanning-tree
-model ('sste') and the curvature regulariser (graph sampling) are outside the accelerated path."""
+KLDiveregenceLoss('sne', inclusive) (objectives.py:48-76) on the kernels of csrc/sne_loss.hip, StochasticTreeLoss its
+spanning-tree model ('sste') on the kernels of csrc/sst_loss.hip; the curvature regulariser (graph sampling) is outside
+the accelerated path."""
 import abc
 import math
 
@@ -215,6 +216,132 @@ class StochasticNeighborLoss(ObjectiveFunction):
         delta = dense(theta_z - theta_x, 0.0)
         mu = (p * delta).sum(dim=1, keepdim=True).detach()
         return log_partition(dz) - log_partition(dx) - (p * (delta - mu)).sum() - mu.sum()
+
+    def __str__(self):
+        return 'kl_loss'
+
+
+class _SstKL(torch.autograd.Function):
+    """Loss and d loss / d mdists from one C-ABI call (mm_sst_kl_loss); the gradient buffer — and with it the inverse of the
+    theta_z model or the G M G products — is asked for only when `mdists` requires a gradient."""
+
+    @staticmethod
+    def forward(ctx, gdists, mdists, mode, alpha):
+        from graphembed import _backend as B
+        B.require_gpu(gdists, mdists)
+        lib = B.lib()
+        n = _nodes_of(mdists.numel())
+        m = mdists.detach().contiguous()
+        g = gdists.detach().to(dtype=m.dtype, device=m.device).contiguous()
+        if g.numel() != m.numel():
+            raise ValueError(f'target has {g.numel()} entries, the pair vector has {m.numel()}')
+        dt = B.dtype_code(m)
+        with B.on_device(m.device):
+            grad = torch.empty_like(m) if ctx.needs_input_grad[1] else None
+            out = torch.empty(1, dtype=m.dtype, device=m.device)
+            ws = torch.empty(lib.raw('mm_sst_kl_ws_bytes')(dt, n), dtype=torch.uint8, device=m.device)
+            lib.call('mm_sst_kl_loss', dt, mode, B.ptr(g), B.ptr(m), n, float(alpha), B.ptr(grad), B.ptr(out), B.ptr(ws),
+                     B.stream_of(m))
+        ctx.grad = None if grad is None else grad.view(mdists.shape)
+        return out[0]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, up):
+        from graphembed import _backend as B
+        return (None, B.take_grads(ctx, up, 'grad')[0], None, None)
+
+
+class _SstTorchOps(torch.autograd.Function):
+    """The closed forms of StochasticTreeLoss with torch ops: loss in forward, the chosen gradient convention in backward
+    (a custom Function, so the route does not depend on what autograd makes of an inverse held outside the graph)."""
+
+    @staticmethod
+    def forward(ctx, gdists, mdists, n, alpha, inclusive, exact):
+        m = mdists.detach()
+        a, b = -alpha * gdists.detach().to(m.dtype), -m
+        tx, tz = (a, b) if inclusive else (b, a)
+        iu = torch.triu_indices(n, n, 1, device=m.device)
+        cx, cz = tx.max(), tz.max()
+
+        def dense(v):
+            full = v.new_zeros((n, n))
+            return full.index_put((torch.cat([iu[0], iu[1]]), torch.cat([iu[1], iu[0]])), torch.cat([v, v]))
+
+        def laplacian(w):
+            off = dense(w)
+            return (torch.diag(off.sum(dim=1)) - off)[1:, 1:]
+
+        def quad(S):   # q(S) per pair, S extended by a zero row and column for node 0
+            full = S.new_zeros((n, n))
+            full[1:, 1:] = S
+            d = torch.diagonal(full)
+            return d[iu[0]] + d[iu[1]] - 2 * full[iu[0], iu[1]]
+
+        def model(w, inverse):
+            """(sum of log pivots x 2, L^-1 or None); a factorisation that fails gives NaN, as the kernels do"""
+            C, info = torch.linalg.cholesky_ex(laplacian(w))
+            C = torch.where(info == 0, C, C.new_full((), math.nan))   # (no host read: the route stays asynchronous)
+            return 2 * torch.log(torch.diagonal(C)).sum(), (torch.cholesky_inverse(C) if inverse else None)
+
+        # shifted weights: exp(theta - max theta); the shifts of A and of mu . delta cancel because sum mu = n - 1
+        wx, wz = torch.exp(tx - cx), torch.exp(tz - cz)
+        delta = (tz - cz) - (tx - cx)
+        need = ctx.needs_input_grad[1]
+        ax, Gx = model(wx, True)
+        az, Gz = model(wz, need and inclusive)
+        mu = wx * quad(Gx)
+        loss = (az - ax) - (mu * delta).sum()
+        if need:
+            if inclusive:
+                grad = mu - wz * quad(Gz)
+            elif exact:
+                grad = mu * delta - wx * quad(Gx @ laplacian(wx * delta) @ Gx)
+            else:
+                grad = mu * (tz - tx)
+            ctx.grad = grad.view(mdists.shape)
+        return loss
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, up):
+        return (None, up * ctx.grad, None, None, None, None)
+
+
+class StochasticTreeLoss(ObjectiveFunction):
+    """KL(trees(theta_x) || trees(theta_z)) of the random-spanning-tree model over pair vectors — the reference's
+    KLDiveregenceLoss('sste', inclusive) (objectives.py:48-76 with inference/stochastic_trees.py): with w = exp theta, L the
+    weighted graph Laplacian without node 0, G = L^-1 and mu_ij = w_ij (G_ii + G_jj - 2 G_ij) the edge marginals,
+        loss = log det L(theta_z) - log det L(theta_x) - mu(theta_x) . (theta_z - theta_x),
+    inclusive: theta_x = -alpha g, theta_z = -m; exclusive: swapped.  `alpha` is a plain float and has no gradient.
+
+    `exact_gradient` matters for the exclusive loss only.  The reference's backward drops d G / d theta there and returns
+    mu (theta_z - theta_x) per pair, which is not the gradient of its loss; False (the default) reproduces that, True gives the
+    gradient of the loss as stated, mu delta - w q(G M G).  Loss, inclusive gradient and exact exclusive gradient do not change
+    when a constant is added to every m; the reference-form gradient does by its definition.
+
+    GPU tensors go through the kernels of csrc/sst_loss.hip (blocked Cholesky and matrix-core products, bitwise reproducible,
+    at most 4096 nodes); CPU tensors, or `native=False`, evaluate the same closed forms with torch ops on dense Laplacians.
+    There is no `fused_spec`: BatchedObjective feeds it `compute_dists`, so it serves every manifold, product and node
+    minibatch.  The determinant couples every pair, so the row-sharded evaluation of graphembed.parallel is not offered."""
+
+    def __init__(self, inclusive=True, native=True, exact_gradient=False):
+        self.inclusive = inclusive
+        self.native = native
+        self.exact_gradient = exact_gradient
+
+    def __call__(self, gdists, mdists, *, epoch=None, alpha):
+        n = _nodes_of(mdists.numel())
+        if gdists.numel() != mdists.numel():
+            raise ValueError(f'target has {gdists.numel()} entries, the pair vector has {mdists.numel()}')
+        if self.native and mdists.is_cuda:
+            from graphembed import _backend as B
+            mode = (B.SST_INCLUSIVE if self.inclusive else B.SST_EXCLUSIVE if self.exact_gradient
+                    else B.SST_EXCLUSIVE_REFERENCE)
+            return _SstKL.apply(gdists, mdists, mode, float(alpha))
+        if n < 2:
+            return mdists.sum() * 0
+        return _SstTorchOps.apply(gdists, mdists, n, float(alpha), bool(self.inclusive), bool(self.exact_gradient))
 
     def __str__(self):
         return 'kl_loss'

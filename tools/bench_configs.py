@@ -14,7 +14,7 @@ import torch  # noqa: E402
 from graphembed import manifolds as M  # noqa: E402
 from graphembed._backend import unit_seed  # noqa: E402
 from graphembed.modules import ManifoldEmbedding  # noqa: E402
-from graphembed.objectives import StochasticNeighborLoss, StressLoss  # noqa: E402
+from graphembed.objectives import StochasticNeighborLoss, StochasticTreeLoss, StressLoss  # noqa: E402
 from graphembed.optim import RiemannianAdam, RiemannianSGD  # noqa: E402
 
 
@@ -57,9 +57,11 @@ def native_case(mans, n, dtype, loss='stress'):
     return {'n': n, 'pairs': P, 'dtype': str(dtype).split('.')[-1], 'step_us': t, 'pairs_per_s': P / (t * 1e-6)}
 
 
-def step_case(mans, n, dtype, fused=False, graph=False, pair_kernel=True, adam=False, sne=None, native=True):
+def step_case(mans, n, dtype, fused=False, graph=False, pair_kernel=True, adam=False, sne=None, sst=None, native=True, batch=None):
     """full training step: compute_dists + stress loss + backward + fused RSGD (momentum 0); `sne` = 'incl' / 'excl': the
-    stochastic-neighbour KL loss instead (alpha = 1), on its kernels or, `native=False`, in its torch-op form"""
+    stochastic-neighbour KL loss instead (alpha = 1), on its kernels or, `native=False`, in its torch-op form; `sst`: the
+    spanning-tree KL loss likewise ('excl' with the reference's gradient, the class's default); `batch`: a fixed index batch of
+    that many nodes through BatchedObjective (the reference's batch_size) instead of the full batch"""
     torch.manual_seed(0)
     torch.set_default_dtype(dtype)
     try:
@@ -71,7 +73,16 @@ def step_case(mans, n, dtype, fused=False, graph=False, pair_kernel=True, adam=F
     P = n * (n - 1) // 2
     target = torch.rand(P, dtype=dtype, device='cuda') * 0.99 + 0.01
     fn = StressLoss() if sne is None else StochasticNeighborLoss(inclusive=sne == 'incl', native=native)
-    kw = {} if sne is None else {'alpha': 1.0}
+    if sst is not None:
+        fn = StochasticTreeLoss(inclusive=sst == 'incl', native=native)
+    kw = {} if sne is None and sst is None else {'alpha': 1.0}
+    if batch is not None:
+        from graphembed.data import GraphDataset
+        from graphembed.modules import BatchedObjective
+        obj = BatchedObjective(fn, GraphDataset(target), emb)
+        obj.check_indices = False   # a slice of a randperm
+        idx = torch.randperm(n, device='cuda')[:batch].clone()
+        P = batch * (batch - 1) // 2
     if adam:  # the optimizer of the paper grid (experiments/run_grid.py:24-36)
         opt = RiemannianAdam(list(emb.xs), lr=1e-3, exact=True, max_grad_norm=20)
         opt_s = RiemannianAdam(list(emb.scales), lr=1e-4, max_grad_norm=500)
@@ -82,7 +93,10 @@ def step_case(mans, n, dtype, fused=False, graph=False, pair_kernel=True, adam=F
     def step():
         opt.zero_grad(set_to_none=True)
         opt_s.zero_grad(set_to_none=True)
-        loss = emb.fused_objective(fn, target, None) if fused else fn(target, emb.compute_dists(None), **kw)
+        if batch is not None:
+            loss = obj(idx, epoch=0, **kw)
+        else:
+            loss = emb.fused_objective(fn, target, None) if fused else fn(target, emb.compute_dists(None), **kw)
         loss.backward(unit_seed(loss))
         opt.step()
         opt_s.step()
@@ -388,6 +402,20 @@ CASES = {
     'stereo2x8_minibatch4096_radam_step_n8192_f32_gathered': lambda: stereo_minibatch_case([2] * 8, 8192, 4096, torch.float32, in_kernel=False),
     'stereo2x8_minibatch4096_radam_step_n8192_f32_gathered_graph': lambda: stereo_minibatch_case([2] * 8, 8192, 4096, torch.float32, graph=True, in_kernel=False),
     'c4_csphd_sne_incl_step_f32_graph': lambda: step_case([M.Lorentz(6), M.Sphere(6), M.SymmetricPositiveDefinite(2)], 1025, torch.float32, sne='incl', graph=True),
+    # spanning-tree KL loss (StochasticTreeLoss: pdist forward over a 512-node index batch, mm_sst_kl_loss, pdist backward) | its torch-op form
+    'c3_spd3_sst_incl_minibatch512_step_n5000_f32': lambda: step_case([M.SymmetricPositiveDefinite(3)], 5000, torch.float32, sst='incl', batch=512),
+    'c3_spd3_sst_incl_minibatch512_step_n5000_f32_torchops': lambda: step_case([M.SymmetricPositiveDefinite(3)], 5000, torch.float32, sst='incl', batch=512, native=False),
+    'c3_spd3_sst_incl_minibatch512_step_n5000_f32_graph': lambda: step_case([M.SymmetricPositiveDefinite(3)], 5000, torch.float32, sst='incl', batch=512, graph=True),
+    'c3_spd3_sst_incl_minibatch512_step_n5000_f64': lambda: step_case([M.SymmetricPositiveDefinite(3)], 5000, torch.float64, sst='incl', batch=512),
+    'c3_spd3_sst_incl_minibatch512_step_n5000_f64_torchops': lambda: step_case([M.SymmetricPositiveDefinite(3)], 5000, torch.float64, sst='incl', batch=512, native=False),
+    'c3_spd3_sst_incl_minibatch512_step_n5000_f64_graph': lambda: step_case([M.SymmetricPositiveDefinite(3)], 5000, torch.float64, sst='incl', batch=512, graph=True),
+    'c3_spd3_sst_excl_minibatch512_step_n5000_f32': lambda: step_case([M.SymmetricPositiveDefinite(3)], 5000, torch.float32, sst='excl', batch=512),
+    'c3_spd3_sst_excl_minibatch512_step_n5000_f32_torchops': lambda: step_case([M.SymmetricPositiveDefinite(3)], 5000, torch.float32, sst='excl', batch=512, native=False),
+    'c3_spd3_sst_excl_minibatch512_step_n5000_f32_graph': lambda: step_case([M.SymmetricPositiveDefinite(3)], 5000, torch.float32, sst='excl', batch=512, graph=True),
+    'c3_spd3_sst_excl_minibatch512_step_n5000_f64': lambda: step_case([M.SymmetricPositiveDefinite(3)], 5000, torch.float64, sst='excl', batch=512),
+    'c3_spd3_sst_excl_minibatch512_step_n5000_f64_torchops': lambda: step_case([M.SymmetricPositiveDefinite(3)], 5000, torch.float64, sst='excl', batch=512, native=False),
+    'c3_spd3_sst_excl_minibatch512_step_n5000_f64_graph': lambda: step_case([M.SymmetricPositiveDefinite(3)], 5000, torch.float64, sst='excl', batch=512, graph=True),
+    'c4_csphd_sst_incl_step_f32_graph': lambda: step_case([M.Lorentz(6), M.Sphere(6), M.SymmetricPositiveDefinite(2)], 1025, torch.float32, sst='incl', graph=True),
 }
 
 
