@@ -348,7 +348,8 @@ enum { MM_GRASSMANN = 0, MM_STIEFEL = 1 };
 enum {
   MM_MAT_PROJU = 0,    /* u - x x^T u (grassmann.py:49-53) / u - x sym(x^T u) (stiefel.py:40-45)   */
   MM_MAT_PROJX = 1,    /* Q of QR(x) (grassmann.py:55-61); Stiefel: sign-fixed (stiefel.py:47-57)  */
-  MM_MAT_RETR_SVD = 2, /* polar factor U V^T of x+u (grassmann.py:76-80, stiefel.py:66-69)         */
+  MM_MAT_RETR_SVD = 2, /* polar factor U V^T of x+u (grassmann.py:76-80, stiefel.py:66-69); St(N, N), the
+                          orthogonal group: followed by one Newton-Schulz step o (3 I - o^T o) / 2       */
   MM_MAT_RETR_QR = 3,  /* Q of QR(x+u) (grassmann.py:71-74); Stiefel sign-fixed (stiefel.py:62-63) */
   MM_MAT_EXP = 4,      /* x V cos(S) V^T + U sin(S) V^T, u = U S V^T (grassmann.py:63-69)          */
   MM_MAT_LOG = 5       /* log_x(u) (grassmann.py:82-89)                                            */
@@ -431,6 +432,51 @@ int mm_mat_rsgd_momentum_step(int dtype, int kind, int retr_op, const void* x, c
 int mm_mat_radam_step(int dtype, int kind, int retr_op, const void* x, const void* egrad, void* exp_avg, void* exp_avg_sq,
                       double* step, unsigned* ticket, int64_t cnt, int N, int p, double lr, double beta1, double beta2,
                       int nc, double eps, double max_grad_norm, int exact, void* x_new, mm_stream_t stream);
+
+/* ---- special orthogonal group SO(N): points are [cnt,N,N], 2 <= N <= mm_so_max_dim() = 4 ---- */
+/* The metric part of the reference's OrthogonalGroup / SpecialOrthogonalGroup (manifolds/orthogonal.py); proju, projx, the
+ * retractions and the fused optimizer steps are those of St(N, N): mm_mat_map and mm_mat_*_step with MM_STIEFEL, p = N.
+ * The distance (orthogonal.py:13-21: sum of the squared arguments of all eigenvalues of x^T y, = ||log(x^T y)||_F^2) is
+ * computed as, and for inputs orthogonal only to rounding DEFINED as, the ambient function
+ *   d2(x, y) = tr psi((y - x)^T (y - x) / 2) = sum_k 4 asin^2(sigma_k / 2),  sigma_k the singular values of y - x,
+ * smooth wherever sigma_k < 2, with the gradient d d2 / dy = B diag(psi'_k) V^T = -d d2 / dx, (y - x) V = B from a one-sided
+ * Jacobi, psi' = 2 theta / sin theta; proju(y, d d2 / dy) = -2 log_y(x).  At the cut locus (a rotation angle of pi: sigma = 2, or
+ * a pair in different components of O(N)) sigma / 2 is clamped to 1 — d2 stays finite — and cos^2(theta / 2) is floored at
+ * 1e-12, so the gradient, undefined there, comes out finite.  The reference's connected-component check (orthogonal.py:14-16)
+ * would synchronise and is not made.
+ * Every entry point validates its arguments before anything touches the GPU: MM_ERR_ARG for null pointers, bad counts or row
+ * ranges and unknown dtypes / ops / loss kinds; MM_ERR_UNSUPPORTED for N outside 2 .. 4.  Nothing allocates, nothing
+ * synchronises: the calls can be captured in a HIP graph. */
+enum {
+  MM_SO_LOG = 0, /* log_x(u), u a point: x skew(x^T D) V diag(theta_k / sin theta_k) V^T, D = u - x (orthogonal.py:26-37, where it
+                    is a loop of scipy.linalg.logm on the CPU) */
+  MM_SO_EXP = 1  /* exp_x(u) = x (V cos(S) V^T + B (sin(S) / S) V^T), skew(x^T u) V = B, S = diag ||b_k|| (the reference has none:
+                    stiefel.py:59-60) */
+};
+int mm_so_max_dim(void);
+int mm_so_map(int dtype, int op, const void* x, const void* u, int64_t cnt, int N, void* out, mm_stream_t stream);
+/* OrthogonalGroup.dist — orthogonal.py:13-21 [sqrt unless squared]; element-wise over cnt pairs; out / (grad_x, grad_y) optional
+ * as in mm_grass_dist (g: upstream gradient per pair, needed with the gradients).  The non-squared gradient of a pair at distance
+ * 0 is 0. */
+int mm_so_dist(int dtype, const void* x, const void* y, const void* g, int64_t cnt, int N, int squared, void* out,
+               void* grad_x, void* grad_y, mm_stream_t stream);
+/* Manifold.pdist default (base.py:59-63) with the distance above, pair order and row-range layout as for mm_grass_pdist_*.
+ * The backward visits every unordered pair of the row range once (csrc/so.hip) and OVERWRITES grad_x [n,N,N] with this shard's
+ * partial gradient; ws: mm_so_pdist_ws_bytes(dtype, n, N), cleared by the call.  n <= 2^30; a forward row range of 2^20 rows or
+ * more is MM_ERR_UNSUPPORTED. */
+size_t mm_so_pdist_ws_bytes(int dtype, int64_t n, int N);
+int mm_so_pdist_fwd(int dtype, const void* x, int64_t n, int N, int64_t row_begin, int64_t row_end, int squared, void* out,
+                    mm_stream_t stream);
+int mm_so_pdist_bwd(int dtype, const void* x, const void* g, int64_t n, int N, int64_t row_begin, int64_t row_end,
+                    int squared, void* grad_x, void* ws, mm_stream_t stream);
+/* Fused objective + gradients of a single-factor SO(N) embedding: mm_grass_pdist_loss without `p` (its header comment applies:
+ * loss kinds, target slice, loss_out = {loss, d loss / d scale_raw}, grad_x overwritten, empty ranges) on m =
+ * softplus(*scale_raw) * d2 with the d2 above — what modules.py:84-88 and objectives.py:16-45 compute for the reference's `so`
+ * factors (experiments/utils.py:3-40), which its own dist cannot differentiate.  ws: mm_so_pdist_loss_ws_bytes(dtype, n, N). */
+size_t mm_so_pdist_loss_ws_bytes(int dtype, int64_t n, int N);
+int mm_so_pdist_loss(int dtype, int loss_kind, const void* x, const void* target, const void* scale_raw, int64_t n, int N,
+                     int64_t row_begin, int64_t row_end, double alpha, double eps, int terms, const double* loss_params,
+                     void* loss_out, void* grad_x, void* ws, mm_stream_t stream);
 
 /* ---- stochastic-neighbour KL objective ---------------------------------------- */
 /* The reference's KLDiveregenceLoss('sne', inclusive) (objectives.py:48-76, inference/stochastic_neighbors.py:8-24) on

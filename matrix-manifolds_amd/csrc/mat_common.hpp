@@ -378,8 +378,28 @@ __device__ __forceinline__ void retr_op(int kind, int op, int N, const T (&xa)[N
   for (int r = 0; r < NP; ++r)
 #pragma unroll
     for (int c = 0; c < P; ++c) y[r][c] = xa[r][c] + ua[r][c];
-  if (op == MM_MAT_RETR_SVD) polar<T, NP, P>(y, o);
-  else if (kind == MM_STIEFEL) qr_q<T, NP, P, true>(y, N, o);
+  if (op == MM_MAT_RETR_SVD) {
+    polar<T, NP, P>(y, o);
+    // St(n, n) is the orthogonal group, where the points carry a metric (so.hip) and their orthogonality is all there is to
+    // being on the manifold: the polar factor comes out with o^T o - I ~ 17 eps (v_rsq, the eigenvalues' rounding and the
+    // drift of the Jacobi vectors, each twice), one Newton-Schulz step o (3 I - o^T o) / 2 squares that and leaves its own
+    // rounding (~3 eps).  o = y M with M symmetric positive definite, so the step moves o towards polar(y) itself.
+    if constexpr (NP == 4) {
+      if (kind == MM_STIEFEL && N == P) {
+        T g[P][P], t[NP][P];
+        gram<T, NP, P>(o, o, g);
+#pragma unroll
+        for (int i = 0; i < P; ++i)
+#pragma unroll
+          for (int j = 0; j < P; ++j) g[i][j] = (i == j ? T(1.5) : T(0)) - T(0.5) * g[i][j];
+        mulr<T, NP, P>(o, g, t);
+#pragma unroll
+        for (int r = 0; r < NP; ++r)
+#pragma unroll
+          for (int c = 0; c < P; ++c) o[r][c] = t[r][c];
+      }
+    }
+  } else if (kind == MM_STIEFEL) qr_q<T, NP, P, true>(y, N, o);
   else qr_q<T, NP, P, false>(y, N, o);
 }
 

@@ -143,7 +143,16 @@ SIGNATURES = {
     'mm_mat_rsgd_momentum_step': (_i, [_i, _i, _i, _vp, _vp, _vp, _i64, _i, _i, _dbl, _dbl, _dbl, _dbl, _i, _vp, _vp]),
     'mm_mat_radam_step': (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _dbl, _dbl, _dbl, _i, _dbl, _dbl, _i, _vp,
                                _vp]),
+    'mm_so_max_dim': (_i, []),
+    'mm_so_map': (_i, [_i, _i, _vp, _vp, _i64, _i, _vp, _vp]),
+    'mm_so_dist': (_i, [_i, _vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp]),
+    'mm_so_pdist_ws_bytes': (_sz, [_i, _i64, _i]),
+    'mm_so_pdist_fwd': (_i, [_i, _vp, _i64, _i, _i64, _i64, _i, _vp, _vp]),
+    'mm_so_pdist_bwd': (_i, [_i, _vp, _vp, _i64, _i, _i64, _i64, _i, _vp, _vp, _vp]),
+    'mm_so_pdist_loss_ws_bytes': (_sz, [_i, _i64, _i]),
+    'mm_so_pdist_loss': (_i, [_i, _i, _vp, _vp, _vp, _i64, _i, _i64, _i64, _dbl, _dbl, _i, _vp, _vp, _vp, _vp, _vp]),
 }
+SO_LOG, SO_EXP = 0, 1  # MM_SO_*
 GRASSMANN, STIEFEL = 0, 1
 SNE_INCLUSIVE, SNE_EXCLUSIVE = 0, 1  # MM_SNE_*
 SST_INCLUSIVE, SST_EXCLUSIVE, SST_EXCLUSIVE_REFERENCE = 0, 1, 2  # MM_SST_*

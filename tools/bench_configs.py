@@ -57,11 +57,16 @@ def native_case(mans, n, dtype, loss='stress'):
     return {'n': n, 'pairs': P, 'dtype': str(dtype).split('.')[-1], 'step_us': t, 'pairs_per_s': P / (t * 1e-6)}
 
 
-def step_case(mans, n, dtype, fused=False, graph=False, pair_kernel=True, adam=False, sne=None, sst=None, native=True, batch=None):
+def step_case(mans, n, dtype, fused=False, graph=False, pair_kernel=True, adam=False, sne=None, sst=None, native=True, batch=None,
+              exact=True, torch_ops=None, iters=20, warm=5):
     """full training step: compute_dists + stress loss + backward + fused RSGD (momentum 0); `sne` = 'incl' / 'excl': the
     stochastic-neighbour KL loss instead (alpha = 1), on its kernels or, `native=False`, in its torch-op form; `sst`: the
     spanning-tree KL loss likewise ('excl' with the reference's gradient, the class's default); `batch`: a fixed index batch of
-    that many nodes through BatchedObjective (the reference's batch_size) instead of the full batch"""
+    that many nodes through BatchedObjective (the reference's batch_size) instead of the full batch; `exact=False`: the manifold's
+    retraction (the fused step kernel where exp has none); `torch_ops`: a function x -> pair vector of squared distances in
+    torch ops that stands in for the manifold's pdist (the yardstick of a factor the reference cannot train; not with `fused` or
+    `batch`)"""
+    assert torch_ops is None or not (fused or batch), 'torch_ops replaces the unfused full-batch pdist'
     torch.manual_seed(0)
     torch.set_default_dtype(dtype)
     try:
@@ -84,10 +89,10 @@ def step_case(mans, n, dtype, fused=False, graph=False, pair_kernel=True, adam=F
         idx = torch.randperm(n, device='cuda')[:batch].clone()
         P = batch * (batch - 1) // 2
     if adam:  # the optimizer of the paper grid (experiments/run_grid.py:24-36)
-        opt = RiemannianAdam(list(emb.xs), lr=1e-3, exact=True, max_grad_norm=20)
+        opt = RiemannianAdam(list(emb.xs), lr=1e-3, exact=exact, max_grad_norm=20)
         opt_s = RiemannianAdam(list(emb.scales), lr=1e-4, max_grad_norm=500)
     else:
-        opt = RiemannianSGD(list(emb.xs), lr=1e-3, exact=True, max_grad_norm=20)
+        opt = RiemannianSGD(list(emb.xs), lr=1e-3, exact=exact, max_grad_norm=20)
         opt_s = RiemannianSGD(list(emb.scales), lr=1e-4, max_grad_norm=500)
 
     def step():
@@ -96,7 +101,12 @@ def step_case(mans, n, dtype, fused=False, graph=False, pair_kernel=True, adam=F
         if batch is not None:
             loss = obj(idx, epoch=0, **kw)
         else:
-            loss = emb.fused_objective(fn, target, None) if fused else fn(target, emb.compute_dists(None), **kw)
+            if fused:
+                loss = emb.fused_objective(fn, target, None)
+            elif torch_ops is not None:
+                loss = fn(target, torch.nn.functional.softplus(emb.scales[0]) * torch_ops(emb.xs[0]), **kw)
+            else:
+                loss = fn(target, emb.compute_dists(None), **kw)
         loss.backward(unit_seed(loss))
         opt.step()
         opt_s.step()
@@ -109,10 +119,35 @@ def step_case(mans, n, dtype, fused=False, graph=False, pair_kernel=True, adam=F
         gr = torch.cuda.CUDAGraph()
         with torch.cuda.graph(gr):
             step()
-        t = timeit(gr.replay)
+        t = timeit(gr.replay, iters, warm)
     else:
-        t = timeit(step)
+        t = timeit(step, iters, warm)
     return {'n': n, 'pairs': P, 'dtype': str(dtype).split('.')[-1], 'step_us': t, 'pairs_per_s': P / (t * 1e-6)}
+
+
+class _SoPdistTorchOps(torch.autograd.Function):
+    """SpecialOrthogonal.pdist(x, squared=True) in torch ops on the GPU — the formulas of csrc/so_pair.hpp on the gathered pairs:
+    D = x_j - x_i = U S V^T (torch.linalg.svd), d2 = sum 4 asin^2(S / 2), d d2 / dx_j = U diag(S psi') V^T.  (Written out: autograd
+    through the SVD divides by differences of singular values, and every rotation plane appears twice.)"""
+
+    @staticmethod
+    def forward(ctx, x):
+        n = x.shape[0]
+        ij = torch.triu_indices(n, n, 1, device=x.device)
+        xd = x.detach()
+        U, S, Vh = torch.linalg.svd(xd[ij[1]] - xd[ij[0]])
+        s = (S / 2).clamp(max=1)
+        half = torch.asin(s)
+        dpsi = 2 * torch.where(s > 1e-20, half / s.clamp_min(1e-20), torch.ones_like(s)) / (1 - s * s).clamp_min(1e-12).sqrt()
+        ctx.save_for_backward(ij, (U * (S * dpsi).unsqueeze(-2)) @ Vh)
+        ctx.n = n
+        return (4 * half * half).sum(-1)
+
+    @staticmethod
+    def backward(ctx, g):
+        ij, dD = ctx.saved_tensors
+        gj = g.reshape(-1, 1, 1) * dD
+        return torch.zeros(ctx.n, *dD.shape[1:], dtype=dD.dtype, device=dD.device).index_add_(0, ij[1], gj).index_add_(0, ij[0], -gj)
 
 
 def stereo_pdist_case(m, n, dtype):
@@ -355,6 +390,15 @@ CASES = {
     'grassmann94_step_n2000_f32': lambda: step_case([M.Grassmann(9, 4)], 2000, torch.float32),
     'grassmann94_step_n2000_f32_fused': lambda: step_case([M.Grassmann(9, 4)], 2000, torch.float32, fused=True),
     'grassmann94_step_n2000_f32_fused_graph': lambda: step_case([M.Grassmann(9, 4)], 2000, torch.float32, fused=True, graph=True),
+    # SO(3) (csrc/so.hip): pdist fwd + bwd; training steps with the retraction (the fused St(n, n) step kernel) on the fused objective,
+    # and the same step with the objective in torch ops on the GPU (batched torch.linalg.svd over the gathered pairs) - the only
+    # yardstick there is: the reference's own dist has no derivative
+    'so3_n2000_f32': lambda: pdist_case(M.SpecialOrthogonal(3), 2000, torch.float32),
+    'so3_step_n2000_f32': lambda: step_case([M.SpecialOrthogonal(3)], 2000, torch.float32, exact=False),
+    'so3_step_n2000_f32_fused': lambda: step_case([M.SpecialOrthogonal(3)], 2000, torch.float32, fused=True, exact=False),
+    'so3_step_n2000_f32_fused_graph': lambda: step_case([M.SpecialOrthogonal(3)], 2000, torch.float32, fused=True, graph=True, exact=False),
+    'so3_step_n2000_f32_torch_ops': lambda: step_case([M.SpecialOrthogonal(3)], 2000, torch.float32, exact=False,
+                                                      torch_ops=_SoPdistTorchOps.apply, iters=3, warm=1),
     # node minibatches with Adam, the reference grid's recipe; `_gathered`: the route before mm_grass_pdist_loss_subset / mm_mat_radam_step
     'grassmann52_minibatch512_radam_step_n2000_f32': lambda: grass_minibatch_case(5, 2, 2000, 512, torch.float32),
     'grassmann52_minibatch512_radam_step_n2000_f32_graph': lambda: grass_minibatch_case(5, 2, 2000, 512, torch.float32, graph=True),
