@@ -580,10 +580,10 @@ __global__ __launch_bounds__(128) void product_step_kernel(PArgs<T> pa, PStep<T>
       spd_momentum_update<T, SD>(xs, gi, b, R.lr, R.momentum, R.dampening, R.max_grad_norm, R.exact, o);
       if (in) store_sym_full<T, SD>(R.state0 + size_t(j) * SD * SD, b);
     } else {
-      T beta2, alpha, mo[NPS];
-      adam_coeffs(R.adam, beta2, alpha);
+      T beta2, alpha, omb1, omb2, mo[NPS];
+      adam_coeffs(R.adam, beta2, alpha, omb1, omb2);
       load_sym_packed<T, SD>(R.state0 + size_t(j) * SD * SD, mo);
-      const T v = spd_adam_update<T, SD>(xs, gi, mo, R.state1[size_t(j) * SD * SD], R.adam, beta2, alpha, o);
+      const T v = spd_adam_update<T, SD>(xs, gi, mo, R.state1[size_t(j) * SD * SD], R.adam, beta2, alpha, omb1, omb2, o);
       if (in) {
         store_sym_full<T, SD>(R.state0 + size_t(j) * SD * SD, mo);
 #pragma unroll
@@ -691,7 +691,8 @@ int product_pairs_t(int loss_kind, int nf, const int* kinds, const int* dims, co
   auto rule_of = [](const mm_step_param& p, VecRuleArgs<T>& r) {
     r = VecRuleArgs<T>{T(p.lr), T(p.momentum), T(p.dampening), T(p.max_grad_norm), p.exact, static_cast<T*>(p.state0),
                        static_cast<T*>(p.state1),
-                       AdamArgs<T>{T(p.lr), T(p.beta1), T(p.beta2), T(p.adam_eps), T(p.max_grad_norm), p.nc, p.exact, p.step, p.ticket}};
+                       AdamArgs<T>{T(p.lr), T(p.beta1), T(p.beta2), T(p.adam_eps), T(p.max_grad_norm), p.nc, p.exact, p.step, p.ticket,
+                                   p.beta1, p.beta2}};
     return p.optimizer == MM_OPT_RADAM ? int(VRULE_ADAM) : (p.momentum != 0.0 ? int(VRULE_MOMENTUM) : int(VRULE_RSGD));
   };
   pa.nf = nf;

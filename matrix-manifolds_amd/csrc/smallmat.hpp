@@ -382,10 +382,15 @@ __device__ __forceinline__ void congr_full(const T (&f)[D * D], const T (&s)[Pac
 // A lane that has converged keeps rotating by ~eps angles, which is harmless; which
 // lanes share a wavefront is fixed by the global column / point index alone (tiles
 // are anchored there), so results do not depend on how the pair list is sharded.
+// OWN = true (the per-point kernels, whose wavefronts hold whatever batch the caller
+// launches): a converged lane sits the remaining sweeps out, so its result is that of
+// its own matrix alone — the same bits at m = 1 and inside a batch
+// (tests/test_spd_point_oracle_gpu.py).  Not for the pair kernels: predicating the
+// unrolled sweeps takes the SPD(4) fp32 backward from 96 to 892 spilled values.
 // tol2 = eps^2 when eigenvectors are used (the residual coupling is then below the
 // rounding already committed in forming A); eigenvalue-only callers may pass eps,
 // because symmetric functions of the spectrum are second-order in the residual.
-template <typename T, int D, bool WITH_V, bool REL = false>
+template <typename T, int D, bool WITH_V, bool REL = false, bool OWN = false>
 __device__ __forceinline__ void jacobi_eig(T (&a)[Packed<D>::NP], T (&v)[D][D], T tol2) {
   using N = Num<T>;
   if (WITH_V) {
@@ -427,6 +432,7 @@ __device__ __forceinline__ void jacobi_eig(T (&a)[Packed<D>::NP], T (&v)[D][D], 
       active = off2 > tol2 * dg2;
     }
     if (!__any(active)) break;
+    if (OWN && !active) continue;
 #pragma unroll
     for (int p = 0; p < D - 1; ++p) {
 #pragma unroll
@@ -464,9 +470,9 @@ __device__ __forceinline__ void jacobi_eig(T (&a)[Packed<D>::NP], T (&v)[D][D], 
     }
   }
 }
-template <typename T, int D, bool WITH_V>
+template <typename T, int D, bool WITH_V, bool OWN = false>
 __device__ __forceinline__ void jacobi_eig(T (&a)[Packed<D>::NP], T (&v)[D][D]) {
-  jacobi_eig<T, D, WITH_V>(a, v, Num<T>::eps() * Num<T>::eps());
+  jacobi_eig<T, D, WITH_V, false, OWN>(a, v, Num<T>::eps() * Num<T>::eps());
 }
 
 // One-sided Jacobi (Hestenes) on a D x D matrix g: on exit b = g V has mutually orthogonal columns, i.e. g = U diag(sigma) V^T

@@ -195,7 +195,7 @@ int mm_spd_radam_step(int dtype, const void* x, const void* egrad, void* exp_avg
                                       static_cast<const T*>(egrad), static_cast<T*>(exp_avg),
                                       static_cast<T*>(exp_avg_sq), m,
                                       AdamArgs<T>{T(lr), T(beta1), T(beta2), T(eps), T(max_grad_norm), nc, exact, step,
-                                                  ticket},
+                                                  ticket, beta1, beta2},
                                       static_cast<T*>(x_new))));
 }
 

@@ -120,7 +120,7 @@ __device__ __attribute__((noinline)) void second_solve_ool(const T* __restrict__
     for (int c = 0; c < D; ++c) out[D + r * D + c] = v[r][c];
 }
 
-template <typename T, int D, bool WITH_V, bool CHOL = false, int SECOND = 1, typename TL>
+template <typename T, int D, bool WITH_V, bool CHOL = false, int SECOND = 1, bool OWN = false, typename TL>
 __device__ __forceinline__ T pair_core(const TL (&li)[Packed<D>::NP], const T (&xj)[Packed<D>::NP], T wmin, T wmax,
                                        T (&w)[D], T (&lw)[D], T (&v)[D][D], T* rho = nullptr) {
   // eigenvalues only: sum log^2 w is second-order in the residual coupling -> tol2 = eps;
@@ -131,7 +131,7 @@ __device__ __forceinline__ T pair_core(const TL (&li)[Packed<D>::NP], const T (&
   {
     T a[Packed<D>::NP];
     pair_a<T, D, CHOL>(li, xj, a);
-    jacobi_eig<T, D, WITH_V, true>(a, v, tol2);
+    jacobi_eig<T, D, WITH_V, true, OWN>(a, v, tol2);   // (OWN: the element-wise kernels, see smallmat.hpp)
 #pragma unroll
     for (int k = 0; k < D; ++k) ev[k] = a[pidx(k, k)];
   }
@@ -1004,13 +1004,11 @@ __global__ void spd_dist_fwd_kernel(const T* __restrict__ x, const T* __restrict
   load_sym_packed<T, D>(y + k * D * D, ys);
   cholesky<T, D>(xs, l);
   invert_lower<T, D>(l, li);
-  T s;
-  if (spd_clamps_wide(wmin, wmax)) {
-    s = pair_value<T, D>(li, ys, wmin, wmax);
-  } else {   // (the eigen-free paths of pair_value do not see eigenvalues: a window that could bind takes the eigensolve)
-    T w[D], lw[D], v[D][D];
-    s = pair_core<T, D, false>(li, ys, wmin, wmax, w, lw, v);
-  }
+  // The eigensolve under every window: pair_value picks its method (series, Cayley, Jacobi) per WAVEFRONT, so a pair's d^2 would
+  // depend on the 63 pairs launched next to it (SPD(3): other bits at m = 1 than inside a batch), and its eigen-free paths do not
+  // see eigenvalues, which a window that can bind needs.
+  T w[D], lw[D], v[D][D];
+  T s = pair_core<T, D, false, false, 1, true>(li, ys, wmin, wmax, w, lw, v);
   s = Num<T>::max(s, wmin);
   if (!squared) s = Num<T>::sqrt(s);
   if (in) out[k] = s;
@@ -1030,7 +1028,7 @@ __global__ void spd_dist_bwd_kernel(const T* __restrict__ x, const T* __restrict
   cholesky<T, D>(xs, l);
   invert_lower<T, D>(l, li);
   T w[D], lw[D], v[D][D], rho[D];
-  const T s = pair_core<T, D, true>(li, ys, wmin, wmax, w, lw, v, rho);
+  const T s = pair_core<T, D, true, false, 1, true>(li, ys, wmin, wmax, w, lw, v, rho);
   T gs = g[k];
   if (!squared) gs *= T(0.5) * Num<T>::rsqrt(Num<T>::max(s, wmin));
   T cm[D], cn[D];
@@ -1087,7 +1085,7 @@ __global__ void spd_map_kernel(int op, const T* __restrict__ x, const T* __restr
     for (int q = 0; q < NP; ++q) o[q] = us[q];
   } else if (op == MM_SPD_PROJX) {
     T v[D][D], f[D];
-    jacobi_eig<T, D, true>(xs, v);
+    jacobi_eig<T, D, true, true>(xs, v);
 #pragma unroll
     for (int q = 0; q < D; ++q) f[q] = Num<T>::min(Num<T>::max(xs[pidx(q, q)], wmin), wmax);
     vdvt<T, D>(v, f, o);
@@ -1133,7 +1131,7 @@ __global__ void spd_eigvalsh_kernel(const T* __restrict__ x, int64_t m, T* __res
   const int64_t k = in ? k0 : 0;
   T a[NP], v[D][D];
   load_sym_packed<T, D>(x + k * D * D, a);
-  jacobi_eig<T, D, false>(a, v);
+  jacobi_eig<T, D, false, true>(a, v);
   T e[D];
 #pragma unroll
   for (int r = 0; r < D; ++r) e[r] = a[pidx(r, r)];
@@ -1191,13 +1189,13 @@ __global__ void spd_radam_step_kernel(const T* x, const T* __restrict__ eg, T* e
   const int64_t k0 = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
   const bool in = k0 < m;
   const int64_t k = in ? k0 : 0;
-  T beta2, alpha;
-  adam_coeffs(a, beta2, alpha);
+  T beta2, alpha, omb1, omb2;
+  adam_coeffs(a, beta2, alpha, omb1, omb2);
   T xs[NP], gs[NP], o[NP], mo[NP];
   load_sym_packed<T, D>(x + k * D * D, xs);
   load_sym_packed<T, D>(eg + k * D * D, gs);
   load_sym_packed<T, D>(exp_avg + k * D * D, mo);
-  const T v = spd_adam_update<T, D>(xs, gs, mo, exp_avg_sq[k * D * D], a, beta2, alpha, o);
+  const T v = spd_adam_update<T, D>(xs, gs, mo, exp_avg_sq[k * D * D], a, beta2, alpha, omb1, omb2, o);
   if (in) {
     store_sym_full<T, D>(xnew + k * D * D, o);
     store_sym_full<T, D>(exp_avg + k * D * D, mo);
@@ -1249,8 +1247,8 @@ __global__ void spd_fused_step_kernel(T* x, int n, StepRule<T> rule, StepFuse<T>
   const int i0 = blockIdx.x * blockDim.x + threadIdx.x;
   const bool in = i0 < n;
   const int i = in ? i0 : 0;
-  T beta2 = T(0), alpha = T(0);
-  if constexpr (RULE == RULE_ADAM) adam_coeffs(rule.adam, beta2, alpha);
+  T beta2 = T(0), alpha = T(0), omb1 = T(0), omb2 = T(0);
+  if constexpr (RULE == RULE_ADAM) adam_coeffs(rule.adam, beta2, alpha, omb1, omb2);
   T xs[NP], gs[NP], o[NP];
   load_sym_packed<T, D>(x + size_t(i) * D * D, xs);
   if constexpr (FIN) {
@@ -1274,7 +1272,7 @@ __global__ void spd_fused_step_kernel(T* x, int n, StepRule<T> rule, StepFuse<T>
   } else {
     T mo[NP];
     load_sym_packed<T, D>(rule.state0 + size_t(i) * D * D, mo);
-    const T v = spd_adam_update<T, D>(xs, gs, mo, rule.state1[size_t(i) * D * D], rule.adam, beta2, alpha, o);
+    const T v = spd_adam_update<T, D>(xs, gs, mo, rule.state1[size_t(i) * D * D], rule.adam, beta2, alpha, omb1, omb2, o);
     if (in) {
       store_sym_full<T, D>(rule.state0 + size_t(i) * D * D, mo);
 #pragma unroll
@@ -1488,7 +1486,8 @@ int spd_fused_step_launch(const mm_train_step* s, Ws<T>& ws, hipStream_t st, boo
   const int n = int(s->n);
   StepRule<T> rule{T(p.lr), T(p.momentum), T(p.dampening), T(p.max_grad_norm), p.exact, static_cast<T*>(p.state0),
                    static_cast<T*>(p.state1),
-                   AdamArgs<T>{T(p.lr), T(p.beta1), T(p.beta2), T(p.adam_eps), T(p.max_grad_norm), p.nc, p.exact, p.step, p.ticket}};
+                   AdamArgs<T>{T(p.lr), T(p.beta1), T(p.beta2), T(p.adam_eps), T(p.max_grad_norm), p.nc, p.exact, p.step, p.ticket,
+                               p.beta1, p.beta2}};
   StepFuse<T> f{ws.nodeL, ws.accM, ws.accS, static_cast<T*>(p.grad),
                 ws.loss, static_cast<const T*>(q.x), static_cast<T*>(s->loss_out),
                 fuse_scale ? static_cast<T*>(q.x) : nullptr, T(q.lr), T(q.max_grad_norm),

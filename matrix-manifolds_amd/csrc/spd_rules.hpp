@@ -40,7 +40,7 @@ __device__ __forceinline__ void spd_explog(const T (&l)[Packed<D>::NP], const T 
                                            const T (&us)[Packed<D>::NP], T (&out)[Packed<D>::NP]) {
   T a[Packed<D>::NP], v[D][D], f[D], fa[Packed<D>::NP];
   congr_lower<T, D>(li, us, a);
-  jacobi_eig<T, D, true>(a, v);
+  jacobi_eig<T, D, true, true>(a, v);   // (OWN: a point's step does not depend on the batch it is launched in)
 #pragma unroll
   for (int k = 0; k < D; ++k) f[k] = IS_LOG ? Num<T>::log(a[pidx(k, k)]) : Num<T>::exp(a[pidx(k, k)]);
   vdvt<T, D>(v, f, fa);
@@ -116,17 +116,17 @@ __device__ __forceinline__ void spd_momentum_update(const T (&xs)[Packed<D>::NP]
 template <typename T, int D>
 __device__ __forceinline__ T spd_adam_update(const T (&xs)[Packed<D>::NP], const T (&gs)[Packed<D>::NP],
                                              T (&mo)[Packed<D>::NP], T vprev, const AdamArgs<T>& a, T beta2, T alpha,
-                                             T (&o)[Packed<D>::NP]) {
+                                             T omb1, T omb2, T (&o)[Packed<D>::NP]) {
   constexpr int NP = Packed<D>::NP;
   T r[NP], l[NP], li[NP];
   const T nn = spd_rgrad_setup<T, D>(xs, gs, r, l, li, true);   // ||r||_X^2 (no floor, unlike Manifold.norm)
   const T nrm = Num<T>::sqrt(nn);
   const T clip = a.max_grad_norm > T(0) ? Num<T>::min(a.max_grad_norm / nrm, T(1)) : T(1);
-  const T v = Num<T>::fma(beta2, vprev, (T(1) - beta2) * nrm * nrm);
+  const T v = Num<T>::fma(beta2, vprev, omb2 * nrm * nrm);   // (omb1 = 1 - beta1, omb2 = 1 - beta2: adam_coeffs)
   const T f = -alpha / (Num<T>::sqrt(v) + a.eps);
 #pragma unroll
   for (int q = 0; q < NP; ++q) {
-    mo[q] = Num<T>::fma(a.beta1, mo[q], (T(1) - a.beta1) * (r[q] * clip));
+    mo[q] = Num<T>::fma(a.beta1, mo[q], omb1 * (r[q] * clip));
     r[q] = mo[q] * f;
   }
   if (a.exact) spd_explog<T, D, false>(l, li, r, o);
