@@ -374,29 +374,33 @@ template <typename T, int D> constexpr int pair_cols_bwd() { return (sizeof(T) =
 // The row loop is unrolled twice with two alternating scalar register sets for the row operand L_i^-1 (no copies), the
 // output row is a running scalar pointer (row i + 1 starts n - i - 2 elements after row i) plus a fixed lane offset:
 // `global_store_dword v_off, v, s[ptr]`, lanes on consecutive j -> 256-B coalesced segments of the row-major pair vector.
+// `shift`: the tiles are those of the problem with `shift` phantom nodes in FRONT (spd_ws.hpp, right_align_shift): the ragged
+// 64 NC columns of a wavefront then sit at the thin end of the triangle.  Only the tile map sees padded indices; from the tile's
+// origin on everything is a real index, and a column below 0 is as dead as one beyond n.
 template <typename T, int D, int TI, bool SQ>
 __global__ __launch_bounds__(kBlock) void spd_pdist_fwd_kernel(const T* __restrict__ nodeL,
                                                                const T* __restrict__ nodeY /* column operand: chol(X_j) */,
                                                                const T* __restrict__ nodeLd /* log det X */, int n, int row_begin,
-                                                               int row_end, T wmin, T wmax, T* __restrict__ out) {
+                                                               int row_end, T wmin, T wmax, T* __restrict__ out, int shift) {
   constexpr int NP = Packed<D>::NP;
   constexpr int NC = pair_cols<T, D>();
   constexpr bool kLd = fwd_uses_logdet<T, D>();   // log det A = nodeLd[j] - nodeLd[i] feeds the far path
   static_assert(TI % 2 == 0, "the row loop is unrolled twice");
-  const TileId tile = fold_tile<TI, kBlock * NC>(n, row_begin, row_end);
+  const TileId tile = fold_tile<TI, kBlock * NC>(n + shift, row_begin + shift, row_end + shift);
   if (!tile.ok) return;
-  const int i0 = tile.i0, i1 = min(i0 + TI, row_end);
+  const int i0 = tile.i0 - shift, i1 = min(i0 + TI, row_end);   // (rows are never phantom: the padded range starts at row `shift`)
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int wave_j0 = tile.jbase + wave * (64 * NC);
+  const int wave_j0 = tile.jbase - shift + wave * (64 * NC);    // (below 0 for the phantom columns of the first block)
   if (wave_j0 + 64 * NC - 1 <= i0) return;  // whole wavefront below the diagonal
+  if (wave_j0 >= n) return;                 // ... or beyond the last column (the unused wavefronts of the last tile)
   int jv[NC];          // column for the validity test (never above a row for lanes beyond n)
   unsigned joff[NC];   // byte offset of the column in a row of the pair vector
   T xj[NC][NP], ldj[NC];
   static_for<NC>([&](auto qc) {
     constexpr int q = decltype(qc)::value;
     const int j = wave_j0 + 64 * q + lane;
-    const bool jin = j < n;
+    const bool jin = unsigned(j) < unsigned(n);   // 0 <= j < n
     jv[q] = jin ? j : INT32_MIN;
     asm volatile("" : "+v"(jv[q]));   // (or the select is undone into `jin && j > row`: a scalar AND per row and column)
     joff[q] = unsigned(j) * unsigned(sizeof(T));
@@ -426,6 +430,7 @@ __global__ __launch_bounds__(kBlock) void spd_pdist_fwd_kernel(const T* __restri
   // (a compare, a saveexec, a branch and a restore per pair) is most of what the loop spends outside the arithmetic.  Most of a
   // launch is interior (all wavefronts of a tile but the one or two on the diagonal and the one on a ragged last column block),
   // so the row loop exists twice and a wavefront picks one on a wave-uniform flag, once.
+  // (wave_j0 >= i1 > 0: no phantom column either)
   const bool interior = wave_j0 >= i1 && wave_j0 + 64 * NC <= n && ((i1 - i0) & 1) == 0;
   auto row_loop = [&](auto masked_c) __attribute__((always_inline)) {
   constexpr bool kMasked = decltype(masked_c)::value;
@@ -1308,15 +1313,15 @@ int spd_pdist_prepare(const T* x, int64_t n, Ws<T>& ws, int flags, hipStream_t s
 constexpr int kFwdTI = 8;   // rows of a forward tile (sweep on MI355X, SPD(3) fp32, n = 5000: 8 / 16 / 32 rows -> 28.8 / 30.1 / 33.0 us)
 template <typename T, int D, int TI>
 int spd_pdist_fwd_launch(const T* nl, const T* nc, const T* nld, int64_t n, int64_t rb, int64_t re, int squared, double wmin, double wmax,
-                         T* out, hipStream_t st) {
+                         T* out, hipStream_t st, int shift) {
   if (!spd_clamps_supported<D, MM_LOSS_NONE>(wmin, wmax)) return MM_ERR_UNSUPPORTED;
-  const dim3 grid = fold_grid<TI, kBlock * pair_cols<T, D>()>(n, rb, re);
+  const dim3 grid = fold_grid<TI, kBlock * pair_cols<T, D>()>(n + shift, rb + shift, re + shift);   // the padded problem's tiles
   if (squared)
     launch_timed(PROF_SPD_FWD, spd_pdist_fwd_kernel<T, D, TI, true>, grid, dim3(kBlock), st, nl, nc, nld, int(n), int(rb), int(re),
-                 T(wmin), T(wmax), out);
+                 T(wmin), T(wmax), out, shift);
   else
     launch_timed(PROF_SPD_FWD, spd_pdist_fwd_kernel<T, D, TI, false>, grid, dim3(kBlock), st, nl, nc, nld, int(n), int(rb), int(re),
-                 T(wmin), T(wmax), out);
+                 T(wmin), T(wmax), out, shift);
   MM_CHECK_LAUNCH();
   return MM_OK;
 }
@@ -1332,12 +1337,15 @@ int spd_pdist_fwd_t(const T* x, int64_t n, int64_t rb, int64_t re, int squared, 
   // A small launch (a rank's shard of a small problem, a small graph) is as long as ONE workgroup's tile: with fewer
   // than ~4 workgroups per CU at 8 rows, tiles of 2 rows make it four times shorter (one eighth of the 5000-node problem:
   // 420 workgroups of 8 rows, 7 us, against 3 us pro rata).  D <= 4 only: the instantiations are not free to compile.
+  // (right-aligned column blocks, spd_ws.hpp: the shift is a function of n and the WAVEFRONT's width alone — dead work is per
+  // wavefront, and which pairs share one must not depend on the row shard)
+  const int shift = right_align_shift(n, 64 * pair_cols<T, D>());
   if constexpr (D <= 4) {
-    const dim3 g8 = fold_grid<kFwdTI, kBlock * pair_cols<T, D>()>(n, rb, re);
+    const dim3 g8 = fold_grid<kFwdTI, kBlock * pair_cols<T, D>()>(n + shift, rb + shift, re + shift);
     if (int64_t(g8.x) * g8.y < 4 * int64_t(device_cus()))
-      return spd_pdist_fwd_launch<T, D, 2>(nl, nc, ws.nodeLd, n, rb, re, squared, wmin, wmax, out, st);
+      return spd_pdist_fwd_launch<T, D, 2>(nl, nc, ws.nodeLd, n, rb, re, squared, wmin, wmax, out, st, shift);
   }
-  return spd_pdist_fwd_launch<T, D, kFwdTI>(nl, nc, ws.nodeLd, n, rb, re, squared, wmin, wmax, out, st);
+  return spd_pdist_fwd_launch<T, D, kFwdTI>(nl, nc, ws.nodeLd, n, rb, re, squared, wmin, wmax, out, st, shift);
 }
 
 // One launch of (at most) the resident capacity; fewer workgroups when the row range is small (>= 8 rows of a column

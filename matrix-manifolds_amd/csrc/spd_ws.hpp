@@ -5,6 +5,7 @@
 
 #include <atomic>
 #include <cstdint>
+#include <cstdlib>
 
 #include "../../include/mm_manifolds.h"
 #include "loss.hpp"
@@ -151,6 +152,22 @@ template <int TI, int BW = kBlock> __device__ __forceinline__ TileId fold_tile(i
     if (x >= cnt) return {0, 0, false};
   }
   return {row_begin + y * TI, (cb0 + x) * BW, true};
+}
+// RIGHT-ALIGNED column blocks (the SPD forward).  Tiles counted from column 0 leave the ragged wavefront — n mod bw live columns
+// of bw = 64 NC — at the THICK end of the triangle, where it runs in every row tile: at n = 5000, bw = 128 the wavefront on the
+// columns 4992 ... 5119 runs in all 625 row tiles with 8 live lanes (13 105 wavefront-tiles in the launch).  The kernel therefore
+// takes its tiles from the PADDED problem — s = right_align_shift(n, bw) phantom nodes in front, n' = n + s a multiple of bw, rows
+// [rb + s, re + s) — and converts at the tile's origin (real index = padded - s).  pair_off(n + s, i + s) = pair_off(n, i) +
+// s (2n - 1 + s) / 2, so the padded problem's pairs (i', j') with j' >= s are exactly the real pairs; rows are never phantom (they
+// start at s), and the ragged wavefront is the first one, alive in one row tile (12 520 wavefront-tiles, -4.46 %).  s depends on n
+// and bw only, never on the row shard: which pairs share a wavefront stays a function of the column alone.
+// The backward's walk (ColWalk below) is NOT right-aligned: measured, it gains nothing (profiles/right_align.md).
+// Phantom nodes in front of a right-aligned problem of n nodes in blocks of bw columns: (bw - n mod bw) mod bw, or 0 where the
+// padded problem would pass the node limit or MM_SPD_SHIFT=0 asks for the plain tiles (A/B within one build; read once).
+inline int right_align_shift(int64_t n, int bw) {
+  static const bool enabled = [] { const char* e = std::getenv("MM_SPD_SHIFT"); return !(e && e[0] == '0'); }();
+  const int64_t s = (bw - n % bw) % bw;
+  return (enabled && n + s <= kSpdMaxNodes) ? int(s) : 0;
 }
 template <int TI, int BW = kBlock> inline dim3 fold_grid(int64_t n, int64_t rb, int64_t re) {
   const int gy = int((re - rb + TI - 1) / TI);
