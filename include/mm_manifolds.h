@@ -477,6 +477,34 @@ size_t mm_so_pdist_loss_ws_bytes(int dtype, int64_t n, int N);
 int mm_so_pdist_loss(int dtype, int loss_kind, const void* x, const void* target, const void* scale_raw, int64_t n, int N,
                      int64_t row_begin, int64_t row_end, double alpha, double eps, int terms, const double* loss_params,
                      void* loss_out, void* grad_x, void* ws, mm_stream_t stream);
+/* The three pair-list entry points above for a NODE MINIBATCH, inside the pair kernels (csrc/so_subset.hip): x is the FULL table
+ * [n_total, N, N]; the points of the step are its rows idx[0..bs) (device int64; the kernels read the low 32 bits and clamp the
+ * node id into [0, n_total)); the pairs are those of the BATCH POSITIONS 0 .. bs in this library's pair order, and row_begin /
+ * row_end shard those positions.  No gather, no scatter-add, no zero fill.
+ *   mm_so_pdist_fwd_subset   writes the batch's pair vector (the slice of the row range) to `out`.
+ *   mm_so_pdist_bwd_subset   g: the upstream gradient of that slice, by batch pair position; grad_x [n_total, N, N] is
+ *                            OVERWRITTEN: rows idx[.] with this shard's partial gradient, every other row with +0.
+ *   mm_so_pdist_loss_subset  mm_grass_pdist_loss_subset without `p` (its header comment applies): the target of batch pair
+ *                            (a, b), a < b, is dense[idx[a]][idx[b]] — exactly that element of the contiguous n_total x n_total
+ *                            matrix, no symmetry assumed; grad_x as above; loss_out = { loss, d loss / d scale_raw }.
+ * For the loss the nodes of a batch must be DISTINCT and bs <= n_total.  For the two pdist entry points REPEATED nodes are allowed
+ * and correct, 0 <= bs <= 2^30: the accumulators are per node and summed with atomics, and a pair of a node with itself has
+ * y - x = 0, hence d = 0 and a zero gradient in the squared and the non-squared form.
+ * ws: mm_so_pdist_ws_bytes / mm_so_pdist_loss_ws_bytes (dtype, n_total, N) — sized by the table, not by the batch, so one buffer
+ * serves every batch and a captured step; each call clears it itself.  A backward / loss call is a memset, the pair kernel (the
+ * accumulators are addressed by node) and the finalize launch over n_total; nothing allocates and nothing synchronises.  bs = 0,
+ * bs = 1 or a row range without pairs launches no pair kernel: the forward writes nothing, the backward a zero gradient, the loss
+ * a zero gradient and {0, 0}.  Errors before anything touches the GPU: MM_ERR_ARG for null pointers (idx, dense, g, out only when
+ * there are pairs), bad counts or row ranges, n_total > 2^30, unknown dtypes / loss kinds and MM_LOSS_NONE as a loss;
+ * MM_ERR_UNSUPPORTED for N outside 2 .. 4, more tiles than one grid dimension holds and a forward row range of 2^20 rows or more. */
+int mm_so_pdist_fwd_subset(int dtype, const void* x, int64_t n_total, int N, const int64_t* idx, int64_t bs,
+                           int64_t row_begin, int64_t row_end, int squared, void* out, mm_stream_t stream);
+int mm_so_pdist_bwd_subset(int dtype, const void* x, const void* g, int64_t n_total, int N, const int64_t* idx, int64_t bs,
+                           int64_t row_begin, int64_t row_end, int squared, void* grad_x, void* ws, mm_stream_t stream);
+int mm_so_pdist_loss_subset(int dtype, int loss_kind, const void* x, const void* dense, const void* scale_raw,
+                            int64_t n_total, int N, const int64_t* idx, int64_t bs, int64_t row_begin, int64_t row_end,
+                            double alpha, double eps, int terms, const double* loss_params, void* loss_out,
+                            void* grad_x, void* ws, mm_stream_t stream);
 
 /* ---- stochastic-neighbour KL objective ---------------------------------------- */
 /* The reference's KLDiveregenceLoss('sne', inclusive) (objectives.py:48-76, inference/stochastic_neighbors.py:8-24) on

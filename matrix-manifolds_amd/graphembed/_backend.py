@@ -151,6 +151,10 @@ SIGNATURES = {
     'mm_so_pdist_bwd': (_i, [_i, _vp, _vp, _i64, _i, _i64, _i64, _i, _vp, _vp, _vp]),
     'mm_so_pdist_loss_ws_bytes': (_sz, [_i, _i64, _i]),
     'mm_so_pdist_loss': (_i, [_i, _i, _vp, _vp, _vp, _i64, _i, _i64, _i64, _dbl, _dbl, _i, _vp, _vp, _vp, _vp, _vp]),
+    'mm_so_pdist_fwd_subset': (_i, [_i, _vp, _i64, _i, _vp, _i64, _i64, _i64, _i, _vp, _vp]),
+    'mm_so_pdist_bwd_subset': (_i, [_i, _vp, _vp, _i64, _i, _vp, _i64, _i64, _i64, _i, _vp, _vp, _vp]),
+    'mm_so_pdist_loss_subset': (_i, [_i, _i, _vp, _vp, _vp, _i64, _i, _vp, _i64, _i64, _i64, _dbl, _dbl, _i, _vp, _vp, _vp, _vp,
+                                     _vp]),
 }
 SO_LOG, SO_EXP = 0, 1  # MM_SO_*
 GRASSMANN, STIEFEL = 0, 1

@@ -3,7 +3,8 @@ SpecialOrthogonalGroup (graphembed/graphembed/manifolds/orthogonal.py:8-44), who
 (no derivative), whose `log` is a loop of scipy.linalg.logm on the CPU and which has no `exp`.
 
 `SpecialOrthogonal(n)` is St(n, n) with a metric: proju, projx, the retractions, rand, randvec and the three fused optimizer
-steps are inherited from `Stiefel`; `dist`, `pdist`, the fused objective `pdist_loss`, `log` and `exp` are new.  The distance is
+steps are inherited from `Stiefel`; `dist`, `pdist`, the fused objective `pdist_loss`, `log` and `exp` are new, and so are the
+node-minibatch forms `pdist_subset` / `pdist_loss_subset` (csrc/so_subset.hip: the index vector inside the pair kernels).  The distance is
 the ambient function d2(x, y) = sum_k 4 asin^2(sigma_k(y - x) / 2) (csrc/so_pair.hpp), equal to ||log(x^T y)||_F^2 on SO(n).
 The reference's connected-component check in `dist` would synchronise and is not made; at the cut locus the distance is finite
 and the gradient (undefined there) is finite.
@@ -117,6 +118,87 @@ class _SoPdistLoss(torch.autograd.Function):
         return gx, gs, None, None, None, None, None
 
 
+def _subset_ws(cache, tag, sizer, x, N):
+    """The workspace of a node-minibatch call: sized by the table and kept in `cache` for the embedding's lifetime (a captured
+    graph of the step refers to it); every call clears it itself."""
+    key = (tag, x.dtype, x.device, x.shape[0], N)
+    ws = cache.get(key) if cache is not None else None
+    if ws is None:
+        ws = torch.empty(B.lib().raw(sizer)(B.dtype_code(x), x.shape[0], N), dtype=torch.uint8, device=x.device)
+        if cache is not None:
+            cache[key] = ws
+    return ws
+
+
+class _SoSubsetLoss(torch.autograd.Function):
+    """Objective and gradients of a node minibatch inside the SO(n) pair kernel (mm_so_pdist_loss_subset): the index vector
+    addresses the rows of the full table, the targets dense[idx[a]][idx[b]] and the gradient rows — no gather, no scatter-add,
+    no zero fill (the sibling of graphembed.manifolds.grassmann._GrassSubsetLoss)."""
+
+    @staticmethod
+    def forward(ctx, spec, rows, N, cache, idx, dense, x, scale):
+        B.require_gpu(x, dense)
+        lkind, alpha, eps, terms = spec[:4]
+        dyn = spec[4] if len(spec) > 4 else None
+        dtype, dev = x.dtype, x.device
+        n_total, bs = x.shape[0], idx.numel()
+        rb, re = (0, bs) if rows is None else rows
+        if dense.dtype != dtype or not dense.is_contiguous() or dense.shape != (n_total, n_total):
+            raise ValueError('dense targets must be a contiguous [n, n] matrix of the embedding\'s dtype')
+        with B.on_device(dev):
+            xc = x.detach().contiguous()
+            sc = scale.detach().to(dtype).reshape(1).contiguous()
+            ic = idx.to(device=dev, dtype=torch.int64).contiguous()
+            out = torch.empty(2, dtype=dtype, device=dev)
+            grad = torch.empty_like(xc)
+            ws = _subset_ws(cache, 'so loss', 'mm_so_pdist_loss_ws_bytes', xc, N)
+            B.lib().call('mm_so_pdist_loss_subset', B.dtype_code(xc), B.LOSS_STRESS if lkind == 'stress' else B.LOSS_QUOTIENT,
+                         B.ptr(xc), B.ptr(dense), B.ptr(sc), n_total, N, B.ptr(ic), bs, rb, re, alpha, eps, terms,
+                         B.dyn_ptr(dyn, x), B.ptr(out), B.ptr(grad), B.ptr(ws), B.stream_of(x))
+        ctx.grads = [grad.reshape(x.shape), out[1].reshape(scale.shape).to(scale.dtype)]
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, up):
+        return (None, None, None, None, None, None) + tuple(B.take_grads(ctx, up, 'grads'))
+
+
+class _SoSubsetPdist(torch.autograd.Function):
+    """The pair vector of a node minibatch of the full table (mm_so_pdist_fwd_subset) and its full-size gradient
+    (mm_so_pdist_bwd_subset): rows outside the batch get +0, repeated nodes accumulate."""
+
+    @staticmethod
+    def forward(ctx, x, idx, N, squared, rows, cache):
+        B.require_gpu(x)
+        xc = x.detach().contiguous()
+        bs = idx.numel()
+        rb, re = (0, bs) if rows is None else rows
+        npairs = B.pair_offset(bs, re) - B.pair_offset(bs, rb) if bs >= 2 else 0
+        with B.on_device(xc.device):
+            ic = idx.to(device=xc.device, dtype=torch.int64).contiguous()
+            out = torch.empty(npairs, dtype=xc.dtype, device=xc.device)
+            if npairs:
+                B.lib().call('mm_so_pdist_fwd_subset', B.dtype_code(xc), B.ptr(xc), xc.shape[0], N, B.ptr(ic), bs, rb, re,
+                             int(squared), B.ptr(out), B.stream_of(xc))
+        ctx.save_for_backward(xc, ic)
+        ctx.args = (N, squared, rb, re, cache, npairs)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        xc, ic = ctx.saved_tensors
+        N, squared, rb, re, cache, npairs = ctx.args
+        if not npairs:
+            return (torch.zeros_like(xc), ) + (None, ) * 5
+        g = g.contiguous()
+        with B.on_device(xc.device):
+            ws = _subset_ws(cache, 'so pdist', 'mm_so_pdist_ws_bytes', xc, N)
+            grad = torch.empty_like(xc)
+            B.lib().call('mm_so_pdist_bwd_subset', B.dtype_code(xc), B.ptr(xc), B.ptr(g), xc.shape[0], N, B.ptr(ic), ic.numel(),
+                         rb, re, int(squared), B.ptr(grad), B.ptr(ws), B.stream_of(xc))
+        return grad, None, None, None, None, None
+
+
 class SpecialOrthogonal(Stiefel):
 
     def __init__(self, n, retr='svd'):
@@ -173,6 +255,26 @@ class SpecialOrthogonal(Stiefel):
         assert x.ndim == 3
         rb, re = (0, x.shape[0]) if rows is None else rows
         return _SoPdistLoss.apply(x, scale, target, self.n, spec, rb, re)
+
+    def subset_form(self, x):
+        """Can the node-minibatch kernels (csrc/so_subset.hip) take the table `x`?  (GPU, fp32 / fp64, [n, N, N], N <= 4.)"""
+        return bool(x.is_cuda and x.dtype in (torch.float32, torch.float64) and x.ndim == 3 and x.shape[0] >= 1
+                    and tuple(x.shape[-2:]) == (self.n, self.n) and 2 <= self.n <= B.lib().raw('mm_so_max_dim')())
+
+    def pdist_loss_subset(self, x, scale, idx, dense, spec, rows=None, cache=None):
+        """`pdist_loss` for the node minibatch `idx` (distinct nodes) of the full table `x` with the targets
+        dense[idx[a], idx[b]], inside the pair kernel; None when the tensors are not eligible (the caller then gathers)."""
+        if not (self.subset_form(x) and dense.is_cuda):
+            return None
+        return _SoSubsetLoss.apply(spec, rows, self.n, cache, idx, dense, x, scale)
+
+    def pdist_subset(self, x, idx, squared=False, rows=None, cache=None):
+        """`pdist(x[idx], squared, rows)` without the gather: the pair vector of the batch from the full table, and in the
+        backward a full-size gradient (rows outside the batch +0).  Repeated nodes are allowed: their gradients accumulate and
+        the pair of a node with itself is 0 with a zero gradient.  None when the tensors are not eligible."""
+        if not self.subset_form(x):
+            return None
+        return _SoSubsetPdist.apply(x, idx, self.n, squared, rows, cache)
 
     def rand_uniform(self, *shape, out=None):  # orthogonal.py:39-44: the first column times the determinant
         xs = super().rand_uniform(*shape, out=out)

@@ -402,9 +402,19 @@ class ManifoldEmbedding(torch.nn.Module):
         """sum_k softplus(s_k) * pdist_k(x_k[i], squared=True) — modules.py:84-88.  (`validated`: see take_rows.)"""
         if i is not None and not validated:
             i = normalise_indices(i, self.n)   # ONE range scan for all factors
-        return sum(
-            softplus(s) * man.pdist(take_rows(x, i, validated=True), squared=True)
-            for x, s, man in zip(self.xs, self.scales, self.manifolds))
+        return sum(softplus(s) * self._factor_pdist(man, x, i) for x, s, man in zip(self.xs, self.scales, self.manifolds))
+
+    def _factor_pdist(self, man, x, i):
+        """Squared pair distances of one factor for the (validated) node minibatch `i`.  A manifold that offers `pdist_subset`
+        (SpecialOrthogonal) takes the index vector inside its pair kernels — no row gather, and no zero fill or scatter-add in
+        the backward; repeated nodes are correct there, so the batch need not be known to be distinct.  Every other factor
+        gathers its rows."""
+        subset = getattr(man, 'pdist_subset', None) if i is not None else None
+        if subset is not None:
+            d2 = subset(x, i, squared=True, cache=self._pair_ws)
+            if d2 is not None:
+                return d2
+        return man.pdist(take_rows(x, i, validated=True), squared=True)
 
     def fused_objective(self, objective_fn, gdists, i=None, rows=None, dense=None, params=None, validated=False, **kwargs):
         """`objective_fn(gdists, self.compute_dists(i), **kwargs)` evaluated by ONE pair kernel
@@ -454,7 +464,7 @@ class ManifoldEmbedding(torch.nn.Module):
                 factor = _single_subset_factor(self.manifolds[0])
                 if factor is not None:
                     return _SingleSubsetLoss.apply(spec, rows, self.manifolds[0], factor, self._pair_ws, i, dense, pts[0], scales[0])
-                # Grassmann: its own pair kernel with the index vector (mm_grass_pdist_loss_subset)
+                # Grassmann, SO(n): their own pair kernels with the index vector (mm_grass_pdist_loss_subset, mm_so_pdist_loss_subset)
                 subset = getattr(self.manifolds[0], 'pdist_loss_subset', None)
                 if subset is not None:
                     loss = subset(pts[0], scales[0], i, dense, spec, rows=rows, cache=self._pair_ws)

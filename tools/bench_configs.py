@@ -317,6 +317,67 @@ def grass_minibatch_case(N, p, n, bs, dtype, graph=False, in_kernel=True):
     return {'n': n, 'pairs': P, 'dtype': str(dtype).split('.')[-1], 'step_us': t, 'pairs_per_s': P / (t * 1e-6)}
 
 
+def so_minibatch_case(N, n, bs, dtype, graph=False, in_kernel=True, sne=False):
+    """node-minibatch training step of an SO(N) embedding with the reference grid's optimizer settings (experiments/run_grid.py:
+    RiemannianAdam(lr=0.01, max_grad_norm=100), batch_size=512) and the retraction (`exact` stays on the optimizers' generic
+    route for SO(n)): objective over the batch + backward + Adam on the points (mm_mat_radam_step either way) and on the scale.
+    `in_kernel`: the index vector inside the pair kernels of csrc/so_subset.hip; otherwise the route before them - the dataset's
+    target gather, `take_rows`, the full-batch kernels on the gathered rows, zero fill and index_add in the backward.  `sne`: the
+    StochasticNeighborLoss on the pair vector of compute_dists (mm_so_pdist_fwd_subset / _bwd_subset) instead of the fused stress
+    objective (mm_so_pdist_loss_subset)"""
+    from graphembed.data import GraphDataset
+    from graphembed.modules import BatchedObjective
+    torch.manual_seed(0)
+    torch.set_default_dtype(dtype)
+    try:
+        with torch.device('cuda'):
+            emb = ManifoldEmbedding(n, [M.SpecialOrthogonal(N)])
+    finally:
+        torch.set_default_dtype(torch.float32)
+    data = GraphDataset(torch.rand(n * (n - 1) // 2, dtype=dtype, device='cuda') * 0.99 + 0.01)
+    if not in_kernel:
+        class Gathered:   # the same targets without the dense matrix on offer
+            __getitem__ = staticmethod(data.__getitem__)
+        data = Gathered()
+        emb.manifolds[0].pdist_subset = None   # compute_dists then gathers its rows
+    obj = BatchedObjective(StochasticNeighborLoss() if sne else StressLoss(), data, emb)
+    kw = dict(alpha=1.0) if sne else {}
+    opt = RiemannianAdam([dict(params=list(emb.xs), lr=0.01, exact=False, max_grad_norm=100), dict(params=list(emb.scales), lr=0.01)])
+    perm = torch.randperm(n, device='cuda')
+    idx = perm[:bs].clone()
+    state = {'i': 0}
+
+    def step():
+        opt.zero_grad(set_to_none=True)
+        loss = obj(idx, **kw)
+        loss.backward(unit_seed(loss))
+        opt.step()
+
+    def advance():
+        i = state['i']
+        idx.copy_(perm[i:i + bs])
+        state['i'] = (i + bs) % max(n - bs, 1)
+    if graph:
+        side = torch.cuda.Stream()
+        with torch.cuda.stream(side):
+            for _ in range(3):
+                step()
+        torch.cuda.current_stream().wait_stream(side)
+        gr = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(gr):
+            step()
+        run = gr.replay
+    else:
+        run = step
+
+    def timed():
+        advance()
+        run()
+    t = timeit(timed, iters=50)
+    P = bs * (bs - 1) // 2
+    return {'n': n, 'pairs': P, 'dtype': str(dtype).split('.')[-1], 'step_us': t, 'pairs_per_s': P / (t * 1e-6)}
+
+
 CASES = {
     'c1_tree40_euclidean10_f64': lambda: pdist_case(M.Euclidean(10), 40, torch.float64),
     'c2_facebook_lorentz11_f32_gram': lambda: pdist_case(M.Lorentz(11), 4039, torch.float32),
@@ -399,6 +460,15 @@ CASES = {
     'so3_step_n2000_f32_fused_graph': lambda: step_case([M.SpecialOrthogonal(3)], 2000, torch.float32, fused=True, graph=True, exact=False),
     'so3_step_n2000_f32_torch_ops': lambda: step_case([M.SpecialOrthogonal(3)], 2000, torch.float32, exact=False,
                                                       torch_ops=_SoPdistTorchOps.apply, iters=3, warm=1),
+    # SO(3) node minibatches with Adam (retraction); `_gathered`: the route before csrc/so_subset.hip; `_sne`: the pair-vector route
+    'so3_minibatch512_radam_step_n2000_f32': lambda: so_minibatch_case(3, 2000, 512, torch.float32),
+    'so3_minibatch512_radam_step_n2000_f32_graph': lambda: so_minibatch_case(3, 2000, 512, torch.float32, graph=True),
+    'so3_minibatch512_radam_step_n2000_f32_gathered': lambda: so_minibatch_case(3, 2000, 512, torch.float32, in_kernel=False),
+    'so3_minibatch512_radam_step_n2000_f32_gathered_graph': lambda: so_minibatch_case(3, 2000, 512, torch.float32, graph=True, in_kernel=False),
+    'so3_minibatch512_sne_radam_step_n2000_f32': lambda: so_minibatch_case(3, 2000, 512, torch.float32, sne=True),
+    'so3_minibatch512_sne_radam_step_n2000_f32_graph': lambda: so_minibatch_case(3, 2000, 512, torch.float32, graph=True, sne=True),
+    'so3_minibatch512_sne_radam_step_n2000_f32_gathered': lambda: so_minibatch_case(3, 2000, 512, torch.float32, in_kernel=False, sne=True),
+    'so3_minibatch512_sne_radam_step_n2000_f32_gathered_graph': lambda: so_minibatch_case(3, 2000, 512, torch.float32, graph=True, in_kernel=False, sne=True),
     # node minibatches with Adam, the reference grid's recipe; `_gathered`: the route before mm_grass_pdist_loss_subset / mm_mat_radam_step
     'grassmann52_minibatch512_radam_step_n2000_f32': lambda: grass_minibatch_case(5, 2, 2000, 512, torch.float32),
     'grassmann52_minibatch512_radam_step_n2000_f32_graph': lambda: grass_minibatch_case(5, 2, 2000, 512, torch.float32, graph=True),
