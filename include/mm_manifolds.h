@@ -477,7 +477,7 @@ size_t mm_so_pdist_loss_ws_bytes(int dtype, int64_t n, int N);
 int mm_so_pdist_loss(int dtype, int loss_kind, const void* x, const void* target, const void* scale_raw, int64_t n, int N,
                      int64_t row_begin, int64_t row_end, double alpha, double eps, int terms, const double* loss_params,
                      void* loss_out, void* grad_x, void* ws, mm_stream_t stream);
-/* The three pair-list entry points above for a NODE MINIBATCH, inside the pair kernels (csrc/so_subset.hip): x is the FULL table
+/* The three pair-list entry points above for a NODE MINIBATCH, inside the pair kernels (csrc/so.hip, SUB): x is the FULL table
  * [n_total, N, N]; the points of the step are its rows idx[0..bs) (device int64; the kernels read the low 32 bits and clamp the
  * node id into [0, n_total)); the pairs are those of the BATCH POSITIONS 0 .. bs in this library's pair order, and row_begin /
  * row_end shard those positions.  No gather, no scatter-add, no zero fill.

@@ -11,6 +11,20 @@
 // The sums go into the transposed workspace acc [N*N][n]; a finalize launch writes grad [n][N][N] (and the loss record).
 // LOSS = MM_LOSS_NONE is the backward of pdist: `target` then holds the upstream gradient of the pair vector and SQUARED says
 // whether that vector held d^2 or d.  The forward writes the pair vector with one store per pair.
+//
+// NODE MINIBATCHES (mm_so_pdist_fwd_subset, mm_so_pdist_bwd_subset, mm_so_pdist_loss_subset) are the same two kernels with SUB,
+// as in grass_loss.hpp: the pairs are those of the BATCH POSITIONS 0 .. bs, the row point is x[node(i)] (wave-uniform: the node id
+// is broadcast to a scalar register, the loads stay scalar), the column point x[node(j)], node(pos) = clamp(low 32 bits of
+// idx[pos], 0, n_total - 1).  The forward writes the batch's pair vector; the symmetric kernel sums into accumulators addressed by
+// NODE, acc [N*N][n_total], and the finalize launch over n_total writes the whole dense gradient: rows outside the batch come out
+// as the +0 the memset left.  No gather, no scatter-add, no zero fill.
+//   LOSS = MM_LOSS_NONE      `target` is the upstream gradient by batch pair position.  Repeated nodes are correct here: the sums
+//                            are per node through atomics, and a pair of a node with itself has D = 0, so d = 0 and a zero
+//                            gradient in the squared and the non-squared form.
+//   STRESS / QUOTIENT        the target of batch pair (a, b), a < b, is dense[node(a)][node(b)]; the nodes of a batch are distinct.
+// The lane's node id is not kept across the row loop: it is re-read where it is needed.  SUB is a template parameter of the
+// kernels themselves and its two arguments trail the others: the SUB = false kernels are, instruction for instruction, the
+// kernels this file had before the minibatch ones joined it (profiles/so_minibatch.md).
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -86,9 +100,15 @@ __global__ __launch_bounds__(64) void so_dist_kernel(const T* __restrict__ x, co
 }
 
 // ------------------------------------------------------------------------------------------------ pair list
-template <typename T, int N>
+// node id of batch position `pos`: the low 32 bits of the index, clamped into the table
+__device__ __forceinline__ int node_of(const int64_t* __restrict__ idx, int pos, int n_total) {
+  return min(max(int(idx[pos]), 0), n_total - 1);
+}
+
+// n: the number of points whose pairs are walked (SUB: the batch size); n_total, idx: SUB only (the table's rows, the batch's nodes)
+template <typename T, int N, bool SUB>
 __global__ __launch_bounds__(kBlk) void so_pdist_fwd_kernel(const T* __restrict__ x, int n, int row_begin, int row_end, int squared,
-                                                            T* __restrict__ out) {
+                                                            T* __restrict__ out, int n_total, const int64_t* __restrict__ idx) {
   const int i0 = row_begin + blockIdx.y * kTI, i1 = min(i0 + kTI, row_end);
   const int jbase = ((i0 + 1) / kBlk + blockIdx.x) * kBlk;
   if (jbase >= n) return;
@@ -96,21 +116,25 @@ __global__ __launch_bounds__(kBlk) void so_pdist_fwd_kernel(const T* __restrict_
   const int j = jbase + threadIdx.x;
   const bool jin = j < n;
   T xj[N][N];
-  load<T, N>(x + size_t(jin ? j : 0) * N * N, xj);
+  if constexpr (SUB) load<T, N>(x + size_t(node_of(idx, jin ? j : 0, n_total)) * N * N, xj);
+  else load<T, N>(x + size_t(jin ? j : 0) * N * N, xj);
   const int64_t base = moff(n, row_begin);
   for (int i = i0; i < i1; ++i) {
     T xi[N][N], D[N][N], dD[N][N];
-    load<T, N>(x + size_t(i) * N * N, xi);  // wave-uniform -> scalar loads
+    int ni = i;
+    if constexpr (SUB) ni = __builtin_amdgcn_readfirstlane(node_of(idx, i, n_total));
+    load<T, N>(x + size_t(ni) * N * N, xi);  // wave-uniform -> scalar loads
     diff<T, N>(xj, xi, D);
     const T v = so_pair<T, N, false>(D, dD);
     if (jin && j > i) out[moff(n, i) - base + (j - i - 1)] = squared ? v : Num<T>::sqrt(v);
   }
 }
 
-template <typename T, int N, int LOSS, bool SQUARED>
+// acc is addressed by point, with SUB by node: [N*N][n or n_total]
+template <typename T, int N, int LOSS, bool SQUARED, bool SUB>
 __global__ __launch_bounds__(64) void so_pdist_sym_kernel(const T* __restrict__ x, const T* __restrict__ target, int n,
                                                           int row_begin, int row_end, int gx, int jb0, LossArgs<T> la,
-                                                          T* __restrict__ acc /* [N*N][n] */) {
+                                                          T* __restrict__ acc, int n_total, const int64_t* __restrict__ idx) {
   static_assert(LOSS == MM_LOSS_NONE || SQUARED, "the objectives are functions of d^2");
   constexpr int GR = group_rows<T, N>(), GV = GR * N;
   __shared__ T red[kTI][N * N];
@@ -129,7 +153,9 @@ __global__ __launch_bounds__(64) void so_pdist_sym_kernel(const T* __restrict__ 
   bool writer;
   const int slot = reduce_slot<GV>(lane, writer);
   T xj[N][N], a[N][N];
-  load<T, N>(x + size_t(jin ? j : 0) * N * N, xj);   // (a lane past the end loads point 0 and contributes nothing)
+  // (a lane past the end loads the point of position 0 and contributes nothing)
+  if constexpr (SUB) load<T, N>(x + size_t(node_of(idx, jin ? j : 0, n_total)) * N * N, xj);
+  else load<T, N>(x + size_t(jin ? j : 0) * N * N, xj);
 #pragma unroll
   for (int r = 0; r < N; ++r)
 #pragma unroll
@@ -139,10 +165,15 @@ __global__ __launch_bounds__(64) void so_pdist_sym_kernel(const T* __restrict__ 
   const int ilast = min(i1, jbase + 63);   // rows from here on have no column in this block
   for (int i = i0; i < ilast; ++i) {
     T xi[N][N], D[N][N], dD[N][N];
-    load<T, N>(x + size_t(i) * N * N, xi);  // wave-uniform -> scalar loads
+    int ni = i;
+    if constexpr (SUB) ni = __builtin_amdgcn_readfirstlane(node_of(idx, i, n_total));
+    load<T, N>(x + size_t(ni) * N * N, xi);  // wave-uniform -> scalar loads
     const bool valid = jin && j > i;
     T tg = LOSS == MM_LOSS_NONE ? T(0) : T(1);
-    if (valid) tg = target[moff(n, i) - base + (j - i - 1)];
+    if (valid) {
+      if constexpr (SUB && LOSS != MM_LOSS_NONE) tg = target[size_t(ni) * size_t(n_total) + size_t(node_of(idx, j, n_total))];
+      else tg = target[moff(n, i) - base + (j - i - 1)];
+    }
     diff<T, N>(xj, xi, D);
     const T v = so_pair<T, N, true>(D, dD);
     T w;
@@ -175,19 +206,22 @@ __global__ __launch_bounds__(64) void so_pdist_sym_kernel(const T* __restrict__ 
     }
   }
   __builtin_amdgcn_wave_barrier();
+  const int na = SUB ? n_total : n;   // accumulator stride
   {
     constexpr int nn = N * N;
     const int cnt = (ilast - i0) * nn;
     for (int t = lane; t < cnt; t += 64) {
       const int il = t / nn, k = t - il * nn;
-      atomic_add(&acc[size_t(k) * n + (i0 + il)], red[il][k]);
+      const int row = SUB ? node_of(idx, i0 + il, n_total) : i0 + il;
+      atomic_add(&acc[size_t(k) * na + row], red[il][k]);
     }
   }
   if (jin) {
+    const int col = SUB ? node_of(idx, j, n_total) : j;
 #pragma unroll
     for (int r = 0; r < N; ++r)
 #pragma unroll
-      for (int c = 0; c < N; ++c) atomic_add(&acc[size_t(r * N + c) * n + j], a[r][c]);
+      for (int c = 0; c < N; ++c) atomic_add(&acc[size_t(r * N + c) * na + col], a[r][c]);
   }
   if constexpr (LOSS != MM_LOSS_NONE) {
     const T ls = wave_sum(loss_acc), dd = wave_sum(ds_acc);
@@ -199,7 +233,8 @@ __global__ __launch_bounds__(64) void so_pdist_sym_kernel(const T* __restrict__ 
   }
 }
 
-// grad [n][nn] from the transposed accumulators; with slots, the first wavefront of block 0 closes the loss record
+// grad [n][nn] from the transposed accumulators (n: the table's rows); with slots, the first wavefront of block 0 closes the loss
+// record
 template <typename T>
 __global__ __launch_bounds__(128) void so_finalize_kernel(const T* __restrict__ acc, int n, int nn, T* __restrict__ grad,
                                                           T* __restrict__ slots, const T* __restrict__ scale_raw,
@@ -215,27 +250,6 @@ inline size_t acc_bytes(int dtype, int64_t n, int N) {
   return (b + 255) & ~size_t(255);
 }
 
-template <typename T, int N, int LOSS, bool SQUARED>
-int launch_sym(const T* x, const T* target, int64_t n, int64_t rb, int64_t re, LossArgs<T> la, T* acc, hipStream_t st) {
-  const int jb0 = int((rb + 1) / 64);
-  const int64_t gx = (n + 63) / 64 - jb0, gy = (re - rb + kTI - 1) / kTI;
-  if (gx <= 0 || gy <= 0) return MM_OK;
-  so_pdist_sym_kernel<T, N, LOSS, SQUARED><<<dim3(unsigned(gx * gy)), dim3(64), 0, st>>>(x, target, int(n), int(rb), int(re),
-                                                                                        int(gx), jb0, la, acc);
-  MMM_CHECK();
-  return MM_OK;
-}
-
-// shared argument checks of the pair-list entry points (before anything touches the GPU)
-inline int check_pairs(int dtype, const void* x, int64_t n, int N, int64_t rb, int64_t re) {
-  if (!x || n < 1 || N < 1 || rb < 0 || re > n || rb > re || n > (1 << 30) || (dtype != MM_F32 && dtype != MM_F64))
-    return MM_ERR_ARG;
-  if (N < 2 || N > kMaxDim) return MM_ERR_UNSUPPORTED;
-  // (the tiles are numbered in one grid dimension)
-  if (((n + 63) / 64) * ((re - rb + kTI - 1) / kTI) > INT32_MAX) return MM_ERR_UNSUPPORTED;
-  return MM_OK;
-}
-
 #define MMSO_DISPATCH_N(N_, ...)                          \
   switch (N_) {                                           \
     case 2: { constexpr int N = 2; __VA_ARGS__ }          \
@@ -243,6 +257,90 @@ inline int check_pairs(int dtype, const void* x, int64_t n, int N, int64_t rb, i
     case 4: { constexpr int N = 4; __VA_ARGS__ }          \
     default: return MM_ERR_UNSUPPORTED;                   \
   }
+
+inline int64_t row_tiles(int64_t rb, int64_t re) { return (re - rb + kTI - 1) / kTI; }
+
+// Shared argument checks of the pair-list entry points (before anything touches the GPU).  n: the points whose pairs are walked,
+// the table itself (n = n_total, n_max = 2^30: the tests on n_total are then the tests n < 1 and n > 2^30) or a batch of it
+// (n_max: 2^30, or n_total where the nodes of a batch are distinct).
+inline int check_pairs(int dtype, const void* x, int64_t n_total, int N, int64_t n, int64_t n_max, int64_t rb, int64_t re) {
+  if (!x || n_total < 1 || n_total > (1 << 30) || N < 1 || n < 0 || n > n_max || rb < 0 || re > n || rb > re ||
+      (dtype != MM_F32 && dtype != MM_F64))
+    return MM_ERR_ARG;
+  if (N < 2 || N > kMaxDim) return MM_ERR_UNSUPPORTED;
+  // (the tiles are numbered in one grid dimension)
+  if (((n + 63) / 64) * row_tiles(rb, re) > INT32_MAX) return MM_ERR_UNSUPPORTED;
+  return MM_OK;
+}
+
+// (false for n < 2 and for a range that is empty or holds only the last row)
+inline bool has_pairs(int64_t n, int64_t rb, int64_t re) { return mm_pair_offset(n, re) > mm_pair_offset(n, rb); }
+
+// the forward launch behind both entry points, after their own checks; null idx: the full batch (n_total = n)
+static int launch_fwd(int dtype, const void* x, int64_t n, int N, int64_t rb, int64_t re, int squared, void* out, int64_t n_total,
+                      const int64_t* idx, hipStream_t st) {
+  const int gx = int((n + kBlk - 1) / kBlk) - int((rb + 1) / kBlk);
+  const int64_t gy = row_tiles(rb, re);
+  if (gx <= 0) return MM_OK;
+  if (gy > 65535) return MM_ERR_UNSUPPORTED;   // (grid.y; a range of 2^20 rows: shard it.  A minibatch has been tested already)
+  const dim3 grid(gx, int(gy));
+  MMM_DISPATCH_T(dtype, MMSO_DISPATCH_N(N, {
+    if (idx) so_pdist_fwd_kernel<T, N, true><<<grid, dim3(kBlk), 0, st>>>(static_cast<const T*>(x), int(n), int(rb), int(re), squared,
+                                                                         static_cast<T*>(out), int(n_total), idx);
+    else so_pdist_fwd_kernel<T, N, false><<<grid, dim3(kBlk), 0, st>>>(static_cast<const T*>(x), int(n), int(rb), int(re), squared,
+                                                                      static_cast<T*>(out), int(n_total), idx);
+    MMM_CHECK(); return MM_OK; }))
+}
+
+// null idx: the full batch (n_total = n)
+template <typename T, int N, int LOSS, bool SQUARED>
+int launch_sym(const T* x, const T* target, int64_t n, int64_t rb, int64_t re, LossArgs<T> la, T* acc, int64_t n_total,
+               const int64_t* idx, hipStream_t st) {
+  const int jb0 = int((rb + 1) / 64);
+  const int64_t gx = (n + 63) / 64 - jb0, gy = row_tiles(rb, re);
+  if (gx <= 0 || gy <= 0) return MM_OK;
+  const dim3 grid(unsigned(gx * gy));
+  if (idx) so_pdist_sym_kernel<T, N, LOSS, SQUARED, true><<<grid, dim3(64), 0, st>>>(x, target, int(n), int(rb), int(re), int(gx), jb0,
+                                                                                    la, acc, int(n_total), idx);
+  else so_pdist_sym_kernel<T, N, LOSS, SQUARED, false><<<grid, dim3(64), 0, st>>>(x, target, int(n), int(rb), int(re), int(gx), jb0,
+                                                                                 la, acc, int(n_total), idx);
+  MMM_CHECK();
+  return MM_OK;
+}
+
+// The backward of the pair vector (loss = MM_LOSS_NONE: `target` is the upstream gradient, no loss record) and the fused objective
+// behind their four entry points, which check and act in the same order: memset, the pair kernel if the range has pairs, the
+// finalize launch over the table.  sub: a node minibatch (n = bs, idx needed where there are pairs); else n_total = n, idx null.
+static int pdist_sym(int dtype, int loss, const void* x, const void* target, const void* scale_raw, int64_t n, int64_t n_max, int N,
+                     int64_t rb, int64_t re, int squared, double alpha, double eps, int terms, const double* loss_params,
+                     void* loss_out, void* grad_x, void* ws, int64_t n_total, const int64_t* idx, bool sub, mm_stream_t stream) {
+  const int rc = check_pairs(dtype, x, n_total, N, n, n_max, rb, re);
+  if (rc != MM_OK) return rc;
+  if (!grad_x || !ws || (loss != MM_LOSS_NONE && !loss_out)) return MM_ERR_ARG;
+  const bool pairs = has_pairs(n, rb, re);
+  if (pairs && (!target || (sub && !idx))) return MM_ERR_ARG;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const size_t slot_bytes = loss == MM_LOSS_NONE ? 0 : 2 * kLossSlots * (dtype == MM_F64 ? 8 : 4);
+  hipError_t e = hipMemsetAsync(ws, 0, acc_bytes(dtype, n_total, N) + slot_bytes, st);
+  if (e != hipSuccess) return int(e);
+  MMM_DISPATCH_T(dtype, MMSO_DISPATCH_N(N, {
+    T* acc = static_cast<T*>(ws);
+    T* slots = loss == MM_LOSS_NONE ? nullptr : reinterpret_cast<T*>(static_cast<char*>(ws) + acc_bytes(dtype, n_total, N));
+    const T* sr = static_cast<const T*>(scale_raw);
+    const T* xs = static_cast<const T*>(x);
+    const T* tg = static_cast<const T*>(target);
+    if (pairs) {
+      LossArgs<T> la{sr, T(alpha), T(eps), terms, slots, loss_params};
+      const int r2 = loss == MM_LOSS_STRESS   ? launch_sym<T, N, MM_LOSS_STRESS, true>(xs, tg, n, rb, re, la, acc, n_total, idx, st)
+                   : loss == MM_LOSS_QUOTIENT ? launch_sym<T, N, MM_LOSS_QUOTIENT, true>(xs, tg, n, rb, re, la, acc, n_total, idx, st)
+                   : squared                  ? launch_sym<T, N, MM_LOSS_NONE, true>(xs, tg, n, rb, re, la, acc, n_total, idx, st)
+                                              : launch_sym<T, N, MM_LOSS_NONE, false>(xs, tg, n, rb, re, la, acc, n_total, idx, st);
+      if (r2 != MM_OK) return r2;
+    }
+    so_finalize_kernel<T><<<dim3(unsigned((n_total + 127) / 128)), dim3(128), 0, st>>>(acc, int(n_total), N * N, static_cast<T*>(grad_x),
+                                                                                      slots, sr, static_cast<T*>(loss_out));
+    MMM_CHECK(); return MM_OK; }))
+}
 
 }  // namespace so
 }  // namespace mm
@@ -290,78 +388,59 @@ size_t mm_so_pdist_ws_bytes(int dtype, int64_t n, int N) {
   return acc_bytes(dtype, n, N);
 }
 
+size_t mm_so_pdist_loss_ws_bytes(int dtype, int64_t n, int N) {
+  if (n < 0 || N < 1) return 0;
+  return acc_bytes(dtype, n, N) + 2 * kLossSlots * (dtype == MM_F64 ? 8 : 4);
+}
+
+// The two forwards keep their own order of checks: a null `out` (MM_ERR_ARG) is tested before the 2^20-row limit
+// (MM_ERR_UNSUPPORTED) for the full batch and after it for a minibatch, and a call can fail both.
 int mm_so_pdist_fwd(int dtype, const void* x, int64_t n, int N, int64_t row_begin, int64_t row_end, int squared, void* out,
                     mm_stream_t stream) {
-  const int rc = check_pairs(dtype, x, n, N, row_begin, row_end);
+  const int rc = check_pairs(dtype, x, n, N, n, 1 << 30, row_begin, row_end);
   if (rc != MM_OK) return rc;
-  if (!out && mm_pair_offset(n, row_end) > mm_pair_offset(n, row_begin)) return MM_ERR_ARG;
+  if (!out && has_pairs(n, row_begin, row_end)) return MM_ERR_ARG;
   if (row_end <= row_begin) return MM_OK;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int gx = int((n + kBlk - 1) / kBlk) - int((row_begin + 1) / kBlk);
-  const int64_t gy = (row_end - row_begin + kTI - 1) / kTI;
-  if (gx <= 0) return MM_OK;
-  if (gy > 65535) return MM_ERR_UNSUPPORTED;   // (grid.y; a range of 2^20 rows: shard it)
-  MMM_DISPATCH_T(dtype, MMSO_DISPATCH_N(N, {
-    so_pdist_fwd_kernel<T, N><<<dim3(gx, int(gy)), dim3(kBlk), 0, st>>>(static_cast<const T*>(x), int(n), int(row_begin),
-                                                                       int(row_end), squared, static_cast<T*>(out));
-    MMM_CHECK(); return MM_OK; }))
+  return launch_fwd(dtype, x, n, N, row_begin, row_end, squared, out, n, nullptr, static_cast<hipStream_t>(stream));
+}
+
+int mm_so_pdist_fwd_subset(int dtype, const void* x, int64_t n_total, int N, const int64_t* idx, int64_t bs, int64_t row_begin,
+                           int64_t row_end, int squared, void* out, mm_stream_t stream) {
+  const int rc = check_pairs(dtype, x, n_total, N, bs, 1 << 30, row_begin, row_end);
+  if (rc != MM_OK) return rc;
+  if (row_tiles(row_begin, row_end) > 65535) return MM_ERR_UNSUPPORTED;
+  if (!has_pairs(bs, row_begin, row_end)) return MM_OK;   // (before the null tests or after: they ask for pairs themselves)
+  if (!idx || !out) return MM_ERR_ARG;
+  return launch_fwd(dtype, x, bs, N, row_begin, row_end, squared, out, n_total, idx, static_cast<hipStream_t>(stream));
 }
 
 int mm_so_pdist_bwd(int dtype, const void* x, const void* g, int64_t n, int N, int64_t row_begin, int64_t row_end, int squared,
                     void* grad_x, void* ws, mm_stream_t stream) {
-  const int rc = check_pairs(dtype, x, n, N, row_begin, row_end);
-  if (rc != MM_OK) return rc;
-  if (!grad_x || !ws) return MM_ERR_ARG;
-  const bool pairs = mm_pair_offset(n, row_end) > mm_pair_offset(n, row_begin);
-  if (!g && pairs) return MM_ERR_ARG;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  hipError_t e = hipMemsetAsync(ws, 0, mm_so_pdist_ws_bytes(dtype, n, N), st);
-  if (e != hipSuccess) return int(e);
-  MMM_DISPATCH_T(dtype, MMSO_DISPATCH_N(N, {
-    T* acc = static_cast<T*>(ws);
-    if (pairs) {
-      LossArgs<T> la{nullptr, T(1), T(0), 0, nullptr, nullptr};
-      const int r2 = squared
-          ? launch_sym<T, N, MM_LOSS_NONE, true>(static_cast<const T*>(x), static_cast<const T*>(g), n, row_begin, row_end, la, acc, st)
-          : launch_sym<T, N, MM_LOSS_NONE, false>(static_cast<const T*>(x), static_cast<const T*>(g), n, row_begin, row_end, la, acc, st);
-      if (r2 != MM_OK) return r2;
-    }
-    so_finalize_kernel<T><<<dim3(unsigned((n + 127) / 128)), dim3(128), 0, st>>>(acc, int(n), N * N, static_cast<T*>(grad_x),
-                                                                                nullptr, nullptr, nullptr);
-    MMM_CHECK(); return MM_OK; }))
+  return pdist_sym(dtype, MM_LOSS_NONE, x, g, nullptr, n, 1 << 30, N, row_begin, row_end, squared, 1.0, 0.0, 0, nullptr, nullptr,
+                   grad_x, ws, n, nullptr, false, stream);
 }
 
-size_t mm_so_pdist_loss_ws_bytes(int dtype, int64_t n, int N) {
-  if (n < 0 || N < 1) return 0;
-  return acc_bytes(dtype, n, N) + 2 * kLossSlots * (dtype == MM_F64 ? 8 : 4);
+int mm_so_pdist_bwd_subset(int dtype, const void* x, const void* g, int64_t n_total, int N, const int64_t* idx, int64_t bs,
+                           int64_t row_begin, int64_t row_end, int squared, void* grad_x, void* ws, mm_stream_t stream) {
+  return pdist_sym(dtype, MM_LOSS_NONE, x, g, nullptr, bs, 1 << 30, N, row_begin, row_end, squared, 1.0, 0.0, 0, nullptr, nullptr,
+                   grad_x, ws, n_total, idx, true, stream);
 }
 
 int mm_so_pdist_loss(int dtype, int loss_kind, const void* x, const void* target, const void* scale_raw, int64_t n, int N,
                      int64_t row_begin, int64_t row_end, double alpha, double eps, int terms, const double* loss_params,
                      void* loss_out, void* grad_x, void* ws, mm_stream_t stream) {
   if (loss_kind != MM_LOSS_STRESS && loss_kind != MM_LOSS_QUOTIENT) return MM_ERR_ARG;
-  const int rc = check_pairs(dtype, x, n, N, row_begin, row_end);
-  if (rc != MM_OK) return rc;
-  if (!grad_x || !ws || !loss_out) return MM_ERR_ARG;
-  const bool pairs = mm_pair_offset(n, row_end) > mm_pair_offset(n, row_begin);
-  if (!target && pairs) return MM_ERR_ARG;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  hipError_t e = hipMemsetAsync(ws, 0, mm_so_pdist_loss_ws_bytes(dtype, n, N), st);
-  if (e != hipSuccess) return int(e);
-  MMM_DISPATCH_T(dtype, MMSO_DISPATCH_N(N, {
-    T* acc = static_cast<T*>(ws);
-    T* slots = reinterpret_cast<T*>(static_cast<char*>(ws) + acc_bytes(dtype, n, N));
-    const T* sr = static_cast<const T*>(scale_raw);
-    if (pairs) {
-      LossArgs<T> la{sr, T(alpha), T(eps), terms, slots, loss_params};
-      const int r2 = loss_kind == MM_LOSS_STRESS
-          ? launch_sym<T, N, MM_LOSS_STRESS, true>(static_cast<const T*>(x), static_cast<const T*>(target), n, row_begin, row_end, la, acc, st)
-          : launch_sym<T, N, MM_LOSS_QUOTIENT, true>(static_cast<const T*>(x), static_cast<const T*>(target), n, row_begin, row_end, la, acc, st);
-      if (r2 != MM_OK) return r2;
-    }
-    so_finalize_kernel<T><<<dim3(unsigned((n + 127) / 128)), dim3(128), 0, st>>>(acc, int(n), N * N, static_cast<T*>(grad_x), slots,
-                                                                                sr, static_cast<T*>(loss_out));
-    MMM_CHECK(); return MM_OK; }))
+  return pdist_sym(dtype, loss_kind, x, target, scale_raw, n, 1 << 30, N, row_begin, row_end, 1, alpha, eps, terms, loss_params,
+                   loss_out, grad_x, ws, n, nullptr, false, stream);
+}
+
+// (the nodes of a batch are distinct: bs <= n_total)
+int mm_so_pdist_loss_subset(int dtype, int loss_kind, const void* x, const void* dense, const void* scale_raw, int64_t n_total, int N,
+                            const int64_t* idx, int64_t bs, int64_t row_begin, int64_t row_end, double alpha, double eps, int terms,
+                            const double* loss_params, void* loss_out, void* grad_x, void* ws, mm_stream_t stream) {
+  if (loss_kind != MM_LOSS_STRESS && loss_kind != MM_LOSS_QUOTIENT) return MM_ERR_ARG;
+  return pdist_sym(dtype, loss_kind, x, dense, scale_raw, bs, n_total, N, row_begin, row_end, 1, alpha, eps, terms, loss_params,
+                   loss_out, grad_x, ws, n_total, idx, true, stream);
 }
 
 }  // extern "C"

@@ -4,7 +4,7 @@ SpecialOrthogonalGroup (graphembed/graphembed/manifolds/orthogonal.py:8-44), who
 
 `SpecialOrthogonal(n)` is St(n, n) with a metric: proju, projx, the retractions, rand, randvec and the three fused optimizer
 steps are inherited from `Stiefel`; `dist`, `pdist`, the fused objective `pdist_loss`, `log` and `exp` are new, and so are the
-node-minibatch forms `pdist_subset` / `pdist_loss_subset` (csrc/so_subset.hip: the index vector inside the pair kernels).  The distance is
+node-minibatch forms `pdist_subset` / `pdist_loss_subset` (csrc/so.hip with SUB: the index vector inside the pair kernels).  The distance is
 the ambient function d2(x, y) = sum_k 4 asin^2(sigma_k(y - x) / 2) (csrc/so_pair.hpp), equal to ||log(x^T y)||_F^2 on SO(n).
 The reference's connected-component check in `dist` would synchronise and is not made; at the cut locus the distance is finite
 and the gradient (undefined there) is finite.
@@ -257,7 +257,7 @@ class SpecialOrthogonal(Stiefel):
         return _SoPdistLoss.apply(x, scale, target, self.n, spec, rb, re)
 
     def subset_form(self, x):
-        """Can the node-minibatch kernels (csrc/so_subset.hip) take the table `x`?  (GPU, fp32 / fp64, [n, N, N], N <= 4.)"""
+        """Can the node-minibatch kernels (csrc/so.hip, SUB) take the table `x`?  (GPU, fp32 / fp64, [n, N, N], N <= 4.)"""
         return bool(x.is_cuda and x.dtype in (torch.float32, torch.float64) and x.ndim == 3 and x.shape[0] >= 1
                     and tuple(x.shape[-2:]) == (self.n, self.n) and 2 <= self.n <= B.lib().raw('mm_so_max_dim')())
 

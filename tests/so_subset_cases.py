@@ -1,4 +1,4 @@
-"""Cases, inputs and the long-double oracle of the SO(n) node-minibatch kernels (csrc/so_subset.hip: mm_so_pdist_fwd_subset,
+"""Cases, inputs and the long-double oracle of the SO(n) node-minibatch kernels (csrc/so.hip with SUB: mm_so_pdist_fwd_subset,
 mm_so_pdist_bwd_subset, mm_so_pdist_loss_subset), under the ABSOLUTE tolerance rule of tests/mat_cases.py (`measure`,
 `Quantity.bound`, `check`, verbatim) with the scales S of tests/so_cases.py.  Host code only; nothing here runs a kernel.
 tests/test_so_subset_host.py walks everything below on the CPU and holds bound_f32 <= CAP S for every compared quantity, with no

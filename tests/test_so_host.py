@@ -208,8 +208,9 @@ def test_so_kernels_keep_everything_in_registers():
     if not (os.path.exists(os.path.join(kernel_meta.LLVM, 'llvm-objdump')) and os.path.exists(kernel_meta.LIB)):
         pytest.skip('needs the ROCm llvm tools and the built library')
     ks = {nm: k for nm, k in kernel_meta.kernels().items() if nm.startswith('so::')}
-    # map, dist, pdist forward: 3 sizes x 2 dtypes each; the pair kernel: x (3 loss kinds + the non-squared backward); 2 finalize
-    assert len(ks) == 3 * 6 + 4 * 6 + 2, sorted(ks)
+    # map, dist: 3 sizes x 2 dtypes each; pdist forward: x 2 (full batch, node minibatch); the pair kernel: x (3 loss kinds + the
+    # non-squared backward) x 2; 2 finalize
+    assert len(ks) == 2 * 6 + 2 * 6 + 2 * 4 * 6 + 2, sorted(ks)
     for nm, k in ks.items():
         assert k['scratch'] == 0 and k['vgpr_spill'] == 0 and k['sgpr_spill'] == 0, (nm, k)
 

@@ -1,4 +1,4 @@
-"""The SO(n) node-minibatch kernels on the GPU (csrc/so_subset.hip: mm_so_pdist_fwd_subset, mm_so_pdist_bwd_subset,
+"""The SO(n) node-minibatch kernels on the GPU (csrc/so.hip with SUB: mm_so_pdist_fwd_subset, mm_so_pdist_bwd_subset,
 mm_so_pdist_loss_subset; SpecialOrthogonal.pdist_subset / pdist_loss_subset and the routes through ManifoldEmbedding.compute_dists,
 fused_objective and BatchedObjective), n = 2 .. 4, fp32 and fp64, against the long-double oracle under the absolute rule of
 tests/mat_cases.py on the cases of tests/so_subset_cases.py (which tests/test_so_subset_host.py holds to bound_f32 <= 1e-3 S on the
@@ -224,6 +224,25 @@ def test_the_full_batch_kernels_on_the_gathered_batch_are_held_to_the_same_quant
                     C.check(f'so gathered pdist {N} {regime} bs={bs}', f'so_subset_pdist_{"d2" if squared else "d"}_{name}', got[name],
                             C.held(q[name]), dname, failures)
     assert not failures, '\n'.join(failures)
+
+
+@pytest.mark.parametrize('dname', DNAMES)
+@pytest.mark.parametrize('N', C.DIMS)
+def test_the_identity_batch_is_the_full_batch_forward_bit_for_bit(N, dname):
+    """idx = 0 .. n_total - 1: the SUB = true and the SUB = false forward walk the same pairs of the same points with the same
+    arithmetic, one store per pair and no atomics.  n_total = 300: a second 256-wide column block, ragged; the row range
+    (17, 200) starts and ends inside a 16-row tile"""
+    n_total = 300
+    x = C.points('spread', n_total, N).to(sc.DT[dname]).cuda()
+    idx = torch.arange(n_total, dtype=torch.int64, device='cuda')
+    for squared in (True, False):
+        for rows in ((0, n_total), (17, 200)):
+            lo, hi = C.pair_slice(n_total, rows)
+            full = _nan(hi - lo, dt=x.dtype)
+            B.lib().call('mm_so_pdist_fwd', B.dtype_code(x), B.ptr(x), n_total, N, rows[0], rows[1], int(squared), B.ptr(full),
+                         B.stream_of(x))
+            sub = abi_fwd(x, idx, squared, rows)
+            assert bool(torch.isfinite(full).all()) and torch.equal(sub, full), (squared, rows)
 
 
 # ---- 4. index hygiene ----------------------------------------------------------------------------------------------------------------

@@ -1,5 +1,5 @@
 """CPU-only checks of the SO(n) node-minibatch kernels (mm_so_pdist_fwd_subset, mm_so_pdist_bwd_subset, mm_so_pdist_loss_subset;
-csrc/so_subset.hip): the tolerance rule of tests/so_subset_cases.py is not vacuous on these cases (bound_f32 <= CAP S for every
+csrc/so.hip with SUB): the tolerance rule of tests/so_subset_cases.py is not vacuous on these cases (bound_f32 <= CAP S for every
 compared quantity), the quotient targets keep their margin from the kinks, the symbols are declared and exported, argument errors
 return before anything touches a GPU, the registers of the new kernels in the built library, and the Python hooks decline CPU
 tensors."""
@@ -132,19 +132,34 @@ def test_the_new_kernels_keep_everything_in_registers():
     sys.path.insert(0, os.path.join(ROOT, 'tools'))
     import kernel_meta
     meta = kernel_meta.kernels()
-    new = {nm: k for nm, k in meta.items() if nm.startswith('so_sub::')}
-    # pdist forward: 3 sizes x 2 dtypes; the pair kernel: x (the squared and the non-squared backward, stress, quotient); 2 finalize
-    assert len(new) == 6 + 24 + 2, sorted(new)
-    assert sum('so_pdist_fwd_kernel' in nm for nm in new) == 6 and sum('so_pdist_sym_kernel' in nm for nm in new) == 24
-    assert sum('so_finalize_kernel' in nm for nm in new) == 2
-    for nm, k in new.items():
+    so = {nm: k for nm, k in meta.items() if re.match(r'so(_\w+)?::', nm)}
+    # pdist forward: 3 sizes x 2 dtypes; the pair kernel: x (the squared and the non-squared backward, stress, quotient); each for
+    # the minibatch (SUB = true) and the full batch; 12 element-wise kernels and 2 finalize: all in so::, no other SO namespace
+    assert len(so) == 2 * (6 + 24) + 12 + 2 and all(nm.startswith('so::') for nm in so), sorted(so)
+    assert sum('so_map_kernel' in nm or 'so_dist_kernel' in nm for nm in so) == 12 and sum('so_finalize_kernel' in nm for nm in so) == 2
+    for sub in ('true', 'false'):
+        assert sum(re.match(rf'so::so_pdist_fwd_kernel<.*, {sub}>$', nm) is not None for nm in so) == 6, sub
+        assert sum(re.match(rf'so::so_pdist_sym_kernel<.*, {sub}>$', nm) is not None for nm in so) == 24, sub
+    for nm, k in so.items():
         assert k['scratch'] == 0 and k['vgpr_spill'] == 0 and k['sgpr_spill'] == 0, (nm, k)
-    for T in ('float', 'double'):
-        for N in (2, 3, 4):
-            for form in ('0, false', '0, true', '1, true', '2, true'):
-                full, sub = meta[f'so::so_pdist_sym_kernel<{T}, {N}, {form}>'], new[f'so_sub::so_pdist_sym_kernel<{T}, {N}, {form}>']
-                assert sub['lds'] == full['lds'], (T, N, form)
-    assert sum(nm.startswith('so::') for nm in meta) == 44   # the full-batch kernels are all still there
+    # vector registers of the 60 pair kernels as (minibatch, full batch): the register table of profiles/so_minibatch.md, recorded
+    # before the two families shared a source
+    forms = ('0, true', '0, false', '1, true', '2, true')   # the table's columns after the forward
+    vgprs = {('float', 2): ((18, 18), (32, 32), (32, 32), (38, 35), (43, 40)),
+             ('float', 3): ((29, 29), (54, 54), (54, 54), (60, 57), (66, 63)),
+             ('float', 4): ((48, 48), (91, 91), (91, 91), (92, 94), (99, 96)),
+             ('double', 2): ((68, 68), (94, 94), (94, 94), (102, 100), (108, 104)),
+             ('double', 3): ((100, 100), (140, 140), (140, 140), (150, 146), (152, 150)),
+             ('double', 4): ((122, 122), (202, 202), (202, 202), (210, 208), (216, 212))}
+    checked = 0
+    for (T, N), row in vgprs.items():
+        names = [f'so::so_pdist_fwd_kernel<{T}, {N}'] + [f'so::so_pdist_sym_kernel<{T}, {N}, {form}' for form in forms]
+        for name, (v_sub, v_full) in zip(names, row):
+            sub, full = so[name + ', true>'], so[name + ', false>']
+            assert (sub['vgpr'], full['vgpr']) == (v_sub, v_full), (name, sub['vgpr'], full['vgpr'])
+            assert sub['lds'] == full['lds'], name
+            checked += 2
+    assert checked == 60
 
 
 # ---- Python --------------------------------------------------------------------------------------------------------------------

@@ -321,7 +321,7 @@ def so_minibatch_case(N, n, bs, dtype, graph=False, in_kernel=True, sne=False):
     """node-minibatch training step of an SO(N) embedding with the reference grid's optimizer settings (experiments/run_grid.py:
     RiemannianAdam(lr=0.01, max_grad_norm=100), batch_size=512) and the retraction (`exact` stays on the optimizers' generic
     route for SO(n)): objective over the batch + backward + Adam on the points (mm_mat_radam_step either way) and on the scale.
-    `in_kernel`: the index vector inside the pair kernels of csrc/so_subset.hip; otherwise the route before them - the dataset's
+    `in_kernel`: the index vector inside the pair kernels of csrc/so.hip (SUB); otherwise the route before them - the dataset's
     target gather, `take_rows`, the full-batch kernels on the gathered rows, zero fill and index_add in the backward.  `sne`: the
     StochasticNeighborLoss on the pair vector of compute_dists (mm_so_pdist_fwd_subset / _bwd_subset) instead of the fused stress
     objective (mm_so_pdist_loss_subset)"""
@@ -460,7 +460,7 @@ CASES = {
     'so3_step_n2000_f32_fused_graph': lambda: step_case([M.SpecialOrthogonal(3)], 2000, torch.float32, fused=True, graph=True, exact=False),
     'so3_step_n2000_f32_torch_ops': lambda: step_case([M.SpecialOrthogonal(3)], 2000, torch.float32, exact=False,
                                                       torch_ops=_SoPdistTorchOps.apply, iters=3, warm=1),
-    # SO(3) node minibatches with Adam (retraction); `_gathered`: the route before csrc/so_subset.hip; `_sne`: the pair-vector route
+    # SO(3) node minibatches with Adam (retraction); `_gathered`: the route before the SUB kernels of csrc/so.hip; `_sne`: the pair-vector route
     'so3_minibatch512_radam_step_n2000_f32': lambda: so_minibatch_case(3, 2000, 512, torch.float32),
     'so3_minibatch512_radam_step_n2000_f32_graph': lambda: so_minibatch_case(3, 2000, 512, torch.float32, graph=True),
     'so3_minibatch512_radam_step_n2000_f32_gathered': lambda: so_minibatch_case(3, 2000, 512, torch.float32, in_kernel=False),
