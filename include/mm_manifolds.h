@@ -175,6 +175,45 @@ int mm_spd_stein_div(int dtype, const void* x, const void* y, const void* g, int
                      int squared, double wmin, void* out, void* grad_x, void* grad_y,
                      mm_stream_t stream);
 
+/* Fused objective + gradients of a Stein-divergence embedding — the counterpart of mm_spd_pdist_loss (same loss kinds,
+ * arguments and outputs; the comments there apply): with S = max(stein divergence of a pair, wmin) — the clamp is on the value
+ * only, spd.py:188,193 — and m = softplus(*scale_raw) * S,
+ *   loss_out = { sum of objective(target, m) over the pairs of rows [row_begin, row_end), d loss / d scale_raw },
+ *   grad_x [n,d,d] OVERWRITTEN with this shard's partial gradient (symmetric; shards sum to the whole).
+ * One pass over the pairs (csrc/spd_stein_loss.hpp): the Cholesky factor of (X_i + X_j)/2 and its inverse feed both points of
+ * the pair, no pair vector is read or written besides `target`.  scale_raw may be NULL (scale 1, loss_out[1] = 0).  Any wmin is
+ * honoured; there is no wmax (the divergence has no eigenvalue window).  ws: mm_spd_pdist_ws_bytes(dtype, n, d); flags /
+ * MM_WS_PREPARED as mm_spd_stein_pdiv_bwd.  Every d = 2 ... mm_spd_max_dim(), fp32 and fp64.  MM_ERR_ARG: null x / ws / grad_x /
+ * loss_out, a null target with a non-empty pair range, a bad row range, n > 2^22, a quotient loss with terms & 3 == 0;
+ * MM_ERR_UNSUPPORTED: another loss kind, d out of range — all before anything is launched.  n == 0 zeroes loss_out; an empty
+ * pair range gives a zero loss record and an all-zero grad_x.  Nothing allocates or synchronises: capture-safe. */
+int mm_spd_stein_pdiv_loss(int dtype, int loss_kind, const void* x, const void* target, const void* scale_raw,
+                           int64_t n, int d, int64_t row_begin, int64_t row_end, double alpha, double eps, int terms,
+                           const double* loss_params, double wmin, void* loss_out, void* grad_x, void* ws, int flags,
+                           mm_stream_t stream);
+/* ... for a NODE MINIBATCH, the counterpart of mm_spd_pdist_loss_subset (the comment there applies, the paragraph on `idx`
+ * included): x is the FULL table [n_total,d,d], the step's points are its rows idx[0 .. bs) (device int64, distinct; the kernel
+ * reads the low 32 bits and clamps the node id into [0, n_total)), the target of batch pair (a, b), a < b, is
+ * dense[idx[a]][idx[b]] — exactly that element of the contiguous n_total x n_total matrix, no symmetry assumed; row_begin /
+ * row_end shard the pair list of the BATCH (0 <= row_begin <= row_end <= bs <= n_total).  grad_x [n_total,d,d] is OVERWRITTEN:
+ * rows idx[.] with this shard's partial gradient, every other row with +0 — no gather, no scatter-add, no zero fill.
+ * ws: mm_spd_pdist_ws_bytes(dtype, n_total, d).  bs < 2 or an empty row range: zero loss record, all-zero grad_x. */
+int mm_spd_stein_pdiv_loss_subset(int dtype, int loss_kind, const void* x, const void* dense, const void* scale_raw,
+                                  int64_t n_total, int d, const int64_t* idx, int64_t bs, int64_t row_begin,
+                                  int64_t row_end, double alpha, double eps, int terms, const double* loss_params,
+                                  double wmin, void* loss_out, void* grad_x, void* ws, int flags, mm_stream_t stream);
+/* mm_spd_stein_pdiv_fwd / _bwd for a node minibatch of the full table (same addressing): `out` / `g` are the pair vector of
+ * the BATCH's rows [row_begin, row_end) (bs (bs - 1) / 2 entries for the whole batch), grad_x [n_total,d,d] is OVERWRITTEN
+ * (+0 outside the batch).  Repeated nodes are allowed HERE: gradients accumulate per node through atomics, and the pair of a
+ * node with itself has S = 0 -> wmin and a gradient w (P - X^-1) / 2 that is zero to rounding (with squared = 0 that rounding is
+ * amplified by 1 / (2 sqrt(wmin)), as in the reference's autograd). */
+int mm_spd_stein_pdiv_fwd_subset(int dtype, const void* x, int64_t n_total, int d, const int64_t* idx, int64_t bs,
+                                 int64_t row_begin, int64_t row_end, int squared, double wmin, void* out, void* ws,
+                                 int flags, mm_stream_t stream);
+int mm_spd_stein_pdiv_bwd_subset(int dtype, const void* x, const void* g, int64_t n_total, int d, const int64_t* idx,
+                                 int64_t bs, int64_t row_begin, int64_t row_end, int squared, double wmin, void* grad_x,
+                                 void* ws, int flags, mm_stream_t stream);
+
 /* Counts the points whose Cholesky factorisation failed in the last prepare of `ws`
  * (n = the point count it was prepared for) into *host_status (0 = all succeeded).
  * Synchronises `stream` — the only blocking call of the ABI. */

@@ -10,7 +10,10 @@ methods, shapes and clamps).  Differences, all documented in DESIGN.md §6:
   autograd returns (the reference reads only one triangle and yields a
   non-symmetric matrix; everything downstream symmetrises it, spd.py:119-135);
 * `use_stein_div=True` rebinds `dist` / `pdist` to the Stein divergence (spd.py:51-53, 183-194, 246-295),
-  also on pair kernels (csrc/spd_stein.hpp); the reference's dense (n, n, d, d) backward is gone.
+  also on pair kernels (csrc/spd_stein.hpp); the reference's dense (n, n, d, d) backward is gone.  Such a manifold also
+  carries `pdist_loss` (the fused objective: loss and gradients from one pass, mm_spd_stein_pdiv_loss) and the node-minibatch
+  forms `pdist_loss_subset` / `pdist_subset` (csrc/spd_stein_loss.hpp: the index vector inside the pair kernels), which
+  ManifoldEmbedding dispatches on.
 """
 import math
 
@@ -276,6 +279,125 @@ class _SteinDiv(torch.autograd.Function):
         return gx.reshape(xs), gy.reshape(ys), None, None, None
 
 
+class _SteinPdivLoss(torch.autograd.Function):
+    """loss(target, softplus(scale) * stein_pdiv(x, squared=True)) and both gradients from ONE pass over the pairs
+    (mm_spd_stein_pdiv_loss) — the sibling of _SpdPdistLoss for the Stein divergence."""
+
+    @staticmethod
+    def forward(ctx, x, scale, target, n_mat, spec, wmin, row_begin, row_end):
+        B.require_gpu(x, target)
+        lib = B.lib()
+        xc = x.detach().contiguous()
+        n = xc.shape[0]
+        dt = B.dtype_code(xc)
+        kind, alpha, eps, terms = spec[:4]
+        dyn = spec[4] if len(spec) > 4 else None  # device {alpha, eps} (QuotientLoss.on_device)
+        tc = target.detach().to(xc.dtype).contiguous()
+        npairs = B.pair_offset(n, row_end) - B.pair_offset(n, row_begin)
+        if tc.numel() != npairs:
+            raise ValueError(f'target has {tc.numel()} entries, the pair range has {npairs}')
+        sc = None if scale is None else scale.detach().to(xc.dtype).reshape(1).contiguous()
+        with B.on_device(xc.device):
+            ws = torch.empty(lib.raw('mm_spd_pdist_ws_bytes')(dt, n, n_mat), dtype=torch.uint8, device=xc.device)
+            out = torch.empty(2, dtype=xc.dtype, device=xc.device)
+            grad = torch.empty_like(xc)
+            lib.call('mm_spd_stein_pdiv_loss', dt, B.LOSS_STRESS if kind == 'stress' else B.LOSS_QUOTIENT, B.ptr(xc), B.ptr(tc),
+                     B.ptr(sc), n, n_mat, row_begin, row_end, alpha, eps, terms, B.dyn_ptr(dyn, xc), wmin, B.ptr(out),
+                     B.ptr(grad), B.ptr(ws), 0, B.stream_of(xc))
+        ctx.grad_x = grad.reshape(x.shape)
+        ctx.grad_s = None if scale is None else out[1].reshape(scale.shape).to(scale.dtype)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, up):
+        gx, gs = B.take_grads(ctx, up, 'grad_x', 'grad_s')
+        return gx, gs, None, None, None, None, None, None
+
+
+def _stein_subset_ws(cache, x, n_mat):
+    """The workspace of a node-minibatch call: sized by the TABLE and kept in `cache` for the embedding's lifetime (a captured
+    graph of the step refers to it); every call prepares it itself."""
+    key = ('stein', x.dtype, x.device, x.shape[0], n_mat)
+    ws = cache.get(key) if cache is not None else None
+    if ws is None:
+        ws = torch.empty(B.lib().raw('mm_spd_pdist_ws_bytes')(B.dtype_code(x), x.shape[0], n_mat), dtype=torch.uint8,
+                         device=x.device)
+        if cache is not None:
+            cache[key] = ws
+    return ws
+
+
+class _SteinSubsetLoss(torch.autograd.Function):
+    """Objective and gradients of a node minibatch inside the Stein pair kernel (mm_spd_stein_pdiv_loss_subset): the index
+    vector addresses the rows of the full table, the targets dense[idx[a]][idx[b]] and the gradient rows — no gather, no
+    scatter-add, no zero fill (the sibling of graphembed.manifolds.special_orthogonal._SoSubsetLoss)."""
+
+    @staticmethod
+    def forward(ctx, spec, rows, n_mat, wmin, cache, idx, dense, x, scale):
+        B.require_gpu(x, dense)
+        lkind, alpha, eps, terms = spec[:4]
+        dyn = spec[4] if len(spec) > 4 else None
+        dtype, dev = x.dtype, x.device
+        n_total, bs = x.shape[0], idx.numel()
+        rb, re = (0, bs) if rows is None else rows
+        if dense.dtype != dtype or not dense.is_contiguous() or dense.shape != (n_total, n_total):
+            raise ValueError('dense targets must be a contiguous [n, n] matrix of the embedding\'s dtype')
+        with B.on_device(dev):
+            xc = x.detach().contiguous()
+            sc = None if scale is None else scale.detach().to(dtype).reshape(1).contiguous()
+            ic = idx.to(device=dev, dtype=torch.int64).contiguous()
+            out = torch.empty(2, dtype=dtype, device=dev)
+            grad = torch.empty_like(xc)
+            ws = _stein_subset_ws(cache, xc, n_mat)
+            B.lib().call('mm_spd_stein_pdiv_loss_subset', B.dtype_code(xc), B.LOSS_STRESS if lkind == 'stress' else B.LOSS_QUOTIENT,
+                         B.ptr(xc), B.ptr(dense), B.ptr(sc), n_total, n_mat, B.ptr(ic), bs, rb, re, alpha, eps, terms,
+                         B.dyn_ptr(dyn, x), wmin, B.ptr(out), B.ptr(grad), B.ptr(ws), 0, B.stream_of(x))
+        ctx.grads = [grad.reshape(x.shape), None if scale is None else out[1].reshape(scale.shape).to(scale.dtype)]
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, up):
+        return (None, None, None, None, None, None, None) + tuple(B.take_grads(ctx, up, 'grads'))
+
+
+class _SteinSubsetPdiv(torch.autograd.Function):
+    """The Stein pair vector of a node minibatch of the full table (mm_spd_stein_pdiv_fwd_subset) and its full-size gradient
+    (mm_spd_stein_pdiv_bwd_subset): rows outside the batch get +0, repeated nodes accumulate."""
+
+    @staticmethod
+    def forward(ctx, x, idx, n_mat, squared, wmin, rows, cache):
+        B.require_gpu(x)
+        xc = x.detach().contiguous()
+        bs = idx.numel()
+        rb, re = (0, bs) if rows is None else rows
+        npairs = B.pair_offset(bs, re) - B.pair_offset(bs, rb) if bs >= 2 else 0
+        with B.on_device(xc.device):
+            ic = idx.to(device=xc.device, dtype=torch.int64).contiguous()
+            out = torch.empty(npairs, dtype=xc.dtype, device=xc.device)
+            if npairs:
+                ws = _stein_subset_ws(cache, xc, n_mat)
+                B.lib().call('mm_spd_stein_pdiv_fwd_subset', B.dtype_code(xc), B.ptr(xc), xc.shape[0], n_mat, B.ptr(ic), bs, rb, re,
+                             int(squared), wmin, B.ptr(out), B.ptr(ws), 0, B.stream_of(xc))
+        ctx.save_for_backward(xc, ic)
+        ctx.args = (n_mat, squared, wmin, rb, re, cache, npairs)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        xc, ic = ctx.saved_tensors
+        n_mat, squared, wmin, rb, re, cache, npairs = ctx.args
+        if not npairs:
+            return (torch.zeros_like(xc), ) + (None, ) * 6
+        g = g.contiguous()
+        with B.on_device(xc.device):
+            # (prepared again: the cached workspace may have served another table of the same shape since the forward)
+            ws = _stein_subset_ws(cache, xc, n_mat)
+            grad = torch.empty_like(xc)
+            B.lib().call('mm_spd_stein_pdiv_bwd_subset', B.dtype_code(xc), B.ptr(xc), B.ptr(g), xc.shape[0], n_mat, B.ptr(ic),
+                         ic.numel(), rb, re, int(squared), wmin, B.ptr(grad), B.ptr(ws), 0, B.stream_of(xc))
+        return grad, None, None, None, None, None, None
+
+
 class SymmetricPositiveDefinite(Manifold):
 
     _warned_narrow = False
@@ -304,7 +426,12 @@ class SymmetricPositiveDefinite(Manifold):
         if use_stein_div:  # spd.py:51-53
             self.dist = self.stein_div
             self.pdist = self.stein_pdiv
-            self.pdist_loss = None  # the fused objective is the affine-invariant one
+            # the fused objective and the node-minibatch forms of the Stein divergence (csrc/spd_stein_loss.hpp), as instance
+            # attributes: a plain SPD manifold gains none of them.  Independent of `clamps_wide`: wmax plays no part in the
+            # divergence and any wmin is honoured as the value clamp.
+            self.pdist_loss = self.stein_pdiv_loss
+            self.pdist_loss_subset = self.stein_pdiv_loss_subset
+            self.pdist_subset = self.stein_pdiv_subset
 
     # -- Vec(.) of Pennec et al. (spd.py:66-81)
     @staticmethod
@@ -505,6 +632,34 @@ class SymmetricPositiveDefinite(Manifold):
         assert x.ndim == 3
         rb, re = (0, x.shape[0]) if rows is None else rows
         return _SteinPdiv.apply(x, self.n, squared, self.wmin, rb, re)
+
+    def stein_pdiv_loss(self, x, scale, target, spec, rows=None):
+        """Fused `objective(target, softplus(scale) * stein_pdiv(x, squared=True))` with its gradients in one pass (`pdist_loss`
+        of a Stein manifold); `scale` may be None (scale 1); `spec` comes from `objective_fn.fused_spec(epoch=, alpha=)`."""
+        assert x.ndim == 3
+        rb, re = (0, x.shape[0]) if rows is None else rows
+        return _SteinPdivLoss.apply(x, scale, target, self.n, spec, self.wmin, rb, re)
+
+    def stein_subset_form(self, x):
+        """Can the Stein node-minibatch kernels take the table `x`?  (GPU, fp32 / fp64, [n, d, d], d within the kernels' range.)"""
+        return bool(x.is_cuda and x.dtype in (torch.float32, torch.float64) and x.ndim == 3 and x.shape[0] >= 1
+                    and tuple(x.shape[-2:]) == (self.n, self.n) and 2 <= self.n <= B.lib().raw('mm_spd_max_dim')())
+
+    def stein_pdiv_loss_subset(self, x, scale, idx, dense, spec, rows=None, cache=None):
+        """`pdist_loss` of a Stein manifold for the node minibatch `idx` (distinct nodes) of the full table `x` with the targets
+        dense[idx[a], idx[b]], inside the pair kernel; None when the tensors are not eligible (the caller then gathers)."""
+        if not (self.stein_subset_form(x) and dense.is_cuda and dense.dtype == x.dtype and dense.is_contiguous()):
+            return None
+        return _SteinSubsetLoss.apply(spec, rows, self.n, self.wmin, cache, idx, dense, x, scale)
+
+    def stein_pdiv_subset(self, x, idx, squared=False, rows=None, cache=None):
+        """`stein_pdiv(x[idx], squared, rows)` without the gather: the pair vector of the batch from the full table, and in the
+        backward a full-size gradient (rows outside the batch +0).  Repeated nodes are allowed: their gradients accumulate per
+        node, and the pair of a node with itself is `wmin` (sqrt of it if not squared) with a gradient that is zero to rounding.
+        None when the tensors are not eligible."""
+        if not self.stein_subset_form(x):
+            return None
+        return _SteinSubsetPdiv.apply(x, idx, self.n, squared, self.wmin, rows, cache)
 
     def transp(self, x, y, u):  # spd.py:196-199
         return u

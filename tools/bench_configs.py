@@ -378,7 +378,77 @@ def so_minibatch_case(N, n, bs, dtype, graph=False, in_kernel=True, sne=False):
     return {'n': n, 'pairs': P, 'dtype': str(dtype).split('.')[-1], 'step_us': t, 'pairs_per_s': P / (t * 1e-6)}
 
 
+def stein_minibatch_case(d, n, bs, dtype, graph=False, in_kernel=True):
+    """node-minibatch training step of a Stein-divergence SPD(d) embedding (the `spdstein` factor of the reference grid) with the
+    grid's optimizer settings, as so_minibatch_case: fused stress objective over the batch + backward + Adam on the points
+    (mm_spd_radam_step either way) and on the scale.  `in_kernel`: the index vector inside the Stein pair kernel
+    (mm_spd_stein_pdiv_loss_subset); otherwise the route before it - the dataset's target gather, `take_rows`, the Stein forward
+    and backward kernels on the gathered rows around mm_product_loss, zero fill and index_add in the backward"""
+    from graphembed.data import GraphDataset
+    from graphembed.modules import BatchedObjective
+    torch.manual_seed(0)
+    torch.set_default_dtype(dtype)
+    try:
+        with torch.device('cuda'):
+            emb = ManifoldEmbedding(n, [M.SymmetricPositiveDefinite(d, use_stein_div=True)])
+    finally:
+        torch.set_default_dtype(torch.float32)
+    data = GraphDataset(torch.rand(n * (n - 1) // 2, dtype=dtype, device='cuda') * 0.01 + 0.001)
+    if not in_kernel:
+        class Gathered:   # the same targets without the dense matrix on offer
+            __getitem__ = staticmethod(data.__getitem__)
+        data = Gathered()
+        man = emb.manifolds[0]
+        man.pdist_loss = man.pdist_loss_subset = man.pdist_subset = None   # the manifold as it was before the fused Stein kernels
+    obj = BatchedObjective(StressLoss(), data, emb)
+    opt = RiemannianAdam([dict(params=list(emb.xs), lr=0.01, exact=False, max_grad_norm=100), dict(params=list(emb.scales), lr=0.01)])
+    perm = torch.randperm(n, device='cuda')
+    idx = perm[:bs].clone()
+    state = {'i': 0}
+
+    def step():
+        opt.zero_grad(set_to_none=True)
+        loss = obj(idx)
+        loss.backward(unit_seed(loss))
+        opt.step()
+
+    def advance():
+        i = state['i']
+        idx.copy_(perm[i:i + bs])
+        state['i'] = (i + bs) % max(n - bs, 1)
+    if graph:
+        side = torch.cuda.Stream()
+        with torch.cuda.stream(side):
+            for _ in range(3):
+                step()
+        torch.cuda.current_stream().wait_stream(side)
+        gr = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(gr):
+            step()
+        run = gr.replay
+    else:
+        run = step
+
+    def timed():
+        advance()
+        run()
+    t = timeit(timed, iters=50)
+    P = bs * (bs - 1) // 2
+    return {'n': n, 'pairs': P, 'dtype': str(dtype).split('.')[-1], 'step_us': t, 'pairs_per_s': P / (t * 1e-6)}
+
+
+def _stein3():
+    return M.SymmetricPositiveDefinite(3, use_stein_div=True)
+
+
 CASES = {
+    'c3_spd3_stein_step_n5000_f32': lambda: step_case([_stein3()], 5000, torch.float32),
+    'c3_spd3_stein_step_n5000_f32_fused': lambda: step_case([_stein3()], 5000, torch.float32, fused=True),
+    'c3_spd3_stein_step_n5000_f32_fused_graph': lambda: step_case([_stein3()], 5000, torch.float32, fused=True, graph=True),
+    'c3_spd3_stein_minibatch512_step_f32': lambda: stein_minibatch_case(3, 5000, 512, torch.float32),
+    'c3_spd3_stein_minibatch512_step_f32_graph': lambda: stein_minibatch_case(3, 5000, 512, torch.float32, graph=True),
+    'c3_spd3_stein_minibatch512_step_f32_gathered': lambda: stein_minibatch_case(3, 5000, 512, torch.float32, in_kernel=False),
+    'c3_spd3_stein_minibatch512_step_f32_gathered_graph': lambda: stein_minibatch_case(3, 5000, 512, torch.float32, graph=True, in_kernel=False),
     'c1_tree40_euclidean10_f64': lambda: pdist_case(M.Euclidean(10), 40, torch.float64),
     'c2_facebook_lorentz11_f32_gram': lambda: pdist_case(M.Lorentz(11), 4039, torch.float32),
     'c2_facebook_lorentz11_f32_valu': lambda: pdist_case(_valu(M.Lorentz(11)), 4039, torch.float32),
