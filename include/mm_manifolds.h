@@ -138,6 +138,45 @@ int mm_spd_pdist_loss(int dtype, int loss_kind, const void* x, const void* targe
                       double alpha, double eps, int terms, const double* loss_params, double wmin, double wmax,
                       void* loss_out, void* grad_x, void* ws, int flags, mm_stream_t stream);
 
+/* ---- SPD(d): the BIT-DETERMINISTIC mode of the two entries above (csrc/spd_det.hpp) ----------------
+ * mm_spd_pdist_bwd and mm_spd_pdist_loss add their row sums, column sums and loss terms with float atomics: two runs on the
+ * same inputs differ in the last bits.  The _det entries compute the same quantities without any atomic — a lane owns a COLUMN
+ * node c and visits every r != c (both orders of a pair, so every logarithm is taken twice), its sums of one chunk of rows
+ * leave with plain stores and a per-node kernel adds a node's chunk records in chunk order — and return the same bits for the
+ * same (dtype, n, d, row range, inputs), on every call: eagerly or replayed from a graph, whatever det_ws held before.
+ *
+ * Geometry (host only, no GPU work): the n rows are cut into `chunks` chunks of `rows_per_chunk` rows,
+ * (chunks - 1) rows_per_chunk < n <= chunks rows_per_chunk; both — and with them every order of summation — are a pure
+ * function of (dtype, n, d): never of the row range, the device, an occupancy query or the environment.  chunks falls as n
+ * grows (the grid is sized towards 1024 workgroups of 256 columns), so the scratch stays bounded:
+ *   mm_spd_pdist_det_ws_bytes = chunks d^2 n sizeof(T)   the slab [chunks][d*d][n]
+ *                             + 2 groups chunks sizeof(T) one {loss, dloss/dsoftplus} slot per workgroup, groups = ceil(n / 256)
+ *   (each part rounded up to 64 bytes), and the slab is at most max(d^2 n sizeof(T), B) with B = 64 MiB.
+ * mm_spd_pdist_det_geometry: MM_ERR_ARG for a dtype other than MM_F32 / MM_F64, n < 1, n > 2^22, d outside 2 ...
+ * mm_spd_max_dim() or null outputs.
+ *
+ * mm_spd_pdist_bwd_det / mm_spd_pdist_loss_det take the arguments of mm_spd_pdist_bwd / mm_spd_pdist_loss plus `det_ws`
+ * (mm_spd_pdist_det_ws_bytes(dtype, n, d) bytes) behind `ws`.  `ws` is the SAME workspace (mm_spd_pdist_ws_bytes): the same
+ * preparation, MM_WS_PREPARED honoured, the status word set for non-PD points (mm_spd_status); its accumulators are not
+ * touched and stay clean, so the same ws serves the atomic entries afterwards.  det_ws may hold anything on entry: every
+ * record the per-node kernel reads is written by the same call.  Capture-safe, no allocation, no synchronisation.
+ * Every d = 2 ... mm_spd_max_dim(), fp32 and fp64; squared and !squared; MM_LOSS_STRESS and MM_LOSS_QUOTIENT.
+ * MM_ERR_ARG: null x / ws / det_ws / grad_x (/ loss_out), null g / target with a non-empty pair range, a row range outside
+ * [0, n], n > 2^22; MM_ERR_UNSUPPORTED: eigenvalue windows narrower than [1e-6, 1e6] (d >= 3, and the fused objective of
+ * every d), as for the atomic entries.  An empty row range: all-zero grad_x, zero loss record.
+ * The loss record is summed per workgroup in a fixed order and over the workgroups' slots in fp64 (lane t of one wavefront
+ * the slots t, t + 64, ... in index order, the 64 lane sums through a fixed butterfly).
+ * Accuracy: the same gates and device functions per pair as the atomic kernel — the two modes agree to rounding. */
+size_t mm_spd_pdist_det_ws_bytes(int dtype, int64_t n, int d);
+int mm_spd_pdist_det_geometry(int dtype, int64_t n, int d, int64_t* chunks, int64_t* rows_per_chunk);
+int mm_spd_pdist_bwd_det(int dtype, const void* x, const void* g, int64_t n, int d,
+                         int64_t row_begin, int64_t row_end, int squared, double wmin,
+                         double wmax, void* grad_x, void* ws, void* det_ws, int flags, mm_stream_t stream);
+int mm_spd_pdist_loss_det(int dtype, int loss_kind, const void* x, const void* target,
+                          const void* scale_raw, int64_t n, int d, int64_t row_begin, int64_t row_end,
+                          double alpha, double eps, int terms, const double* loss_params, double wmin, double wmax,
+                          void* loss_out, void* grad_x, void* ws, void* det_ws, int flags, mm_stream_t stream);
+
 /* The same objective for a NODE MINIBATCH, with no gather or scatter launch around it (train.py:198-222 draws
  * idx = randperm(n)[a:b]; ManifoldEmbedding.compute_dists(idx) gathers x[idx], modules.py:86; GraphDataset.__getitem__
  * gathers dense[idx][:, idx], data/dataset.py:19-27; autograd's index backward scatters the gradient rows):

@@ -82,6 +82,12 @@ SIGNATURES = {
     'mm_spd_pdist_bwd': (_i, [_i, _vp, _vp, _i64, _i, _i64, _i64, _i, _dbl, _dbl, _vp, _vp, _i, _vp]),
     'mm_spd_pdist_loss': (_i, [_i, _i, _vp, _vp, _vp, _i64, _i, _i64, _i64, _dbl, _dbl, _i, _vp, _dbl, _dbl, _vp, _vp,
                                 _vp, _i, _vp]),
+    # the bit-deterministic mode (csrc/spd_det.hpp): the atomic entries' arguments plus `det_ws` behind `ws`
+    'mm_spd_pdist_det_ws_bytes': (_sz, [_i, _i64, _i]),
+    'mm_spd_pdist_det_geometry': (_i, [_i, _i64, _i, _c.POINTER(_i64), _c.POINTER(_i64)]),
+    'mm_spd_pdist_bwd_det': (_i, [_i, _vp, _vp, _i64, _i, _i64, _i64, _i, _dbl, _dbl, _vp, _vp, _vp, _i, _vp]),
+    'mm_spd_pdist_loss_det': (_i, [_i, _i, _vp, _vp, _vp, _i64, _i, _i64, _i64, _dbl, _dbl, _i, _vp, _dbl, _dbl, _vp, _vp,
+                                    _vp, _vp, _i, _vp]),
     'mm_spd_pdist_loss_subset': (_i, [_i, _i, _vp, _vp, _vp, _i64, _i, _vp, _i64, _i64, _i64, _dbl, _dbl, _i, _vp, _dbl, _dbl,
                                        _vp, _vp, _vp, _i, _vp]),
     'mm_vec_pdist_loss_subset': (_i, [_i, _i, _i, _vp, _vp, _vp, _i64, _i, _vp, _i64, _i64, _i64, _dbl, _dbl, _i, _vp, _vp, _vp,

@@ -80,7 +80,65 @@ class _SpdPdist(torch.autograd.Function):
         return grad, None, None, None, None, None, None, None
 
 
-_GATHER_BYTES = 256 << 20   # budget of one gathered chunk (both sides) of the narrow-window pdist below
+def _det_ws(cache, x, n_mat):
+    """The scratch of the bit-deterministic pair kernels (mm_spd_pdist_det_ws_bytes: chunk records and loss slots), kept in
+    `cache` per (dtype, device, n): a captured step refers to it and does not allocate.  It may hold anything between calls."""
+    key = (x.dtype, x.device, x.shape[0])
+    ws = cache.get(key)
+    if ws is None:
+        ws = torch.empty(B.lib().raw('mm_spd_pdist_det_ws_bytes')(B.dtype_code(x), x.shape[0], n_mat), dtype=torch.uint8,
+                         device=x.device)
+        cache[key] = ws
+    return ws
+
+
+class _SpdPdistDet(torch.autograd.Function):
+    """_SpdPdist with the backward of the bit-deterministic mode (mm_spd_pdist_bwd_det: no float atomics; the forward kernel
+    has none anyway).  Hosted in Python: the C++ autograd node issues the atomic pair of calls only."""
+
+    @staticmethod
+    def forward(ctx, x, n_mat, squared, wmin, wmax, row_begin, row_end, check_pd, cache):
+        B.require_gpu(x)
+        lib = B.lib()
+        xc = x.detach().contiguous()
+        n = xc.shape[0]
+        dt = B.dtype_code(xc)
+        npairs = B.pair_offset(n, row_end) - B.pair_offset(n, row_begin)
+        ctx.empty = npairs == 0
+        ctx.save_for_backward(xc)
+        if ctx.empty:
+            return xc.new_empty(0)
+        with B.on_device(xc.device):
+            ws = torch.empty(lib.raw('mm_spd_pdist_ws_bytes')(dt, n, n_mat), dtype=torch.uint8, device=xc.device)
+            out = torch.empty(npairs, dtype=xc.dtype, device=xc.device)
+            lib.call('mm_spd_pdist_fwd', dt, B.ptr(xc), n, n_mat, row_begin, row_end, int(squared),
+                     wmin, wmax, B.ptr(out), B.ptr(ws), 0, B.stream_of(xc))
+            if check_pd:
+                import ctypes
+                st = ctypes.c_int(0)
+                lib.call('mm_spd_status', B.ptr(ws), n, ctypes.byref(st), B.stream_of(xc))
+                if st.value:
+                    raise torch.linalg.LinAlgError(f'pdist: {st.value} input matrices are not positive-definite')
+        ctx.ws, ctx.cache = ws, cache
+        ctx.args = (n_mat, squared, wmin, wmax, row_begin, row_end)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        xc, = ctx.saved_tensors
+        if ctx.empty:
+            return (torch.zeros_like(xc), ) + (None, ) * 8
+        n_mat, squared, wmin, wmax, row_begin, row_end = ctx.args
+        g = g.contiguous()
+        with B.on_device(xc.device):
+            grad = torch.empty_like(xc)
+            B.lib().call('mm_spd_pdist_bwd_det', B.dtype_code(xc), B.ptr(xc), B.ptr(g), xc.shape[0], n_mat, row_begin, row_end,
+                         int(squared), wmin, wmax, B.ptr(grad), B.ptr(ctx.ws), B.ptr(_det_ws(ctx.cache, xc, n_mat)),
+                         B.MM_WS_PREPARED, B.stream_of(xc))
+        return (grad, ) + (None, ) * 8
+
+
+_GATHER_BYTES = 256 << 20  # budget of one gathered chunk (both sides) of the narrow-window pdist below
 
 
 def _pair_row_chunks(n, rb, re, max_pairs, device):
@@ -181,6 +239,41 @@ class _SpdPdistLoss(torch.autograd.Function):
     def backward(ctx, up):
         gx, gs = B.take_grads(ctx, up, 'grad_x', 'grad_s')
         return gx, gs, None, None, None, None, None, None, None
+
+
+class _SpdPdistLossDet(torch.autograd.Function):
+    """_SpdPdistLoss in the bit-deterministic mode (mm_spd_pdist_loss_det): the same loss record and gradients without a float
+    atomic — the same bits on every call."""
+
+    @staticmethod
+    def forward(ctx, x, scale, target, n_mat, spec, wmin, wmax, row_begin, row_end, cache):
+        B.require_gpu(x, target)
+        lib = B.lib()
+        xc = x.detach().contiguous()
+        n = xc.shape[0]
+        dt = B.dtype_code(xc)
+        kind, alpha, eps, terms = spec[:4]
+        dyn = spec[4] if len(spec) > 4 else None  # device {alpha, eps} (QuotientLoss.on_device)
+        tc = target.detach().to(xc.dtype).contiguous()
+        npairs = B.pair_offset(n, row_end) - B.pair_offset(n, row_begin)
+        if tc.numel() != npairs:
+            raise ValueError(f'target has {tc.numel()} entries, the pair range has {npairs}')
+        sc = None if scale is None else scale.detach().to(xc.dtype).reshape(1).contiguous()
+        with B.on_device(xc.device):
+            ws = torch.empty(lib.raw('mm_spd_pdist_ws_bytes')(dt, n, n_mat), dtype=torch.uint8, device=xc.device)
+            out = torch.empty(2, dtype=xc.dtype, device=xc.device)
+            grad = torch.empty_like(xc)
+            lib.call('mm_spd_pdist_loss_det', dt, B.LOSS_STRESS if kind == 'stress' else B.LOSS_QUOTIENT,
+                     B.ptr(xc), B.ptr(tc), B.ptr(sc), n, n_mat, row_begin, row_end, alpha, eps, terms, B.dyn_ptr(dyn, xc),
+                     wmin, wmax, B.ptr(out), B.ptr(grad), B.ptr(ws), B.ptr(_det_ws(cache, xc, n_mat)), 0, B.stream_of(xc))
+        ctx.grad_x = grad
+        ctx.grad_s = None if scale is None else out[1].reshape(scale.shape).to(scale.dtype)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, up):
+        gx, gs = B.take_grads(ctx, up, 'grad_x', 'grad_s')
+        return (gx, gs) + (None, ) * 8
 
 
 class _SpdDist(torch.autograd.Function):
@@ -403,7 +496,20 @@ class SymmetricPositiveDefinite(Manifold):
     _warned_narrow = False
 
     def __init__(self, n, *, fast_symeig=True, fast_chol=True, use_stein_div=False, wmin=1e-8,
-                 wmax=1e8, check_pd=False):
+                 wmax=1e8, check_pd=False, deterministic=None):
+        """`deterministic`: True — the gradients of `pdist` and the fused objective `pdist_loss` come from the bit-deterministic
+        pair kernels (mm_spd_pdist_bwd_det / mm_spd_pdist_loss_det: no float atomics, the same bits on every call, about two
+        logarithms per pair instead of one); False — the atomic kernels; None (default) — follows
+        torch.are_deterministic_algorithms_enabled() at call time."""
+        if deterministic and use_stein_div:
+            raise ValueError('SymmetricPositiveDefinite(use_stein_div=True, deterministic=True): the Stein-divergence kernels '
+                             'have no bit-deterministic mode (they accumulate with float atomics)')
+        if deterministic and n >= 3 and not (wmin <= 1e-6 and wmax >= 1e6):
+            raise ValueError(f'SymmetricPositiveDefinite({n}, wmin={wmin:g}, wmax={wmax:g}, deterministic=True): eigenvalue '
+                             'clamps narrower than [1e-6, 1e6] run off the pair kernels (gathered pairs, scatter-added '
+                             'gradients) and have no bit-deterministic mode')
+        self.deterministic = deterministic
+        self._det_ws = {}   # scratch of the deterministic kernels per (dtype, device, n): see _det_ws
         self.n = n
         self.wmin = wmin
         self.wmax = wmax
@@ -588,6 +694,14 @@ class SymmetricPositiveDefinite(Manifold):
         return self._map(B.SPD_LOG, x, y)
 
     # -- distances -------------------------------------------------------------
+    def is_deterministic(self):
+        """Do `pdist` / `pdist_loss` take the bit-deterministic kernels now?  `deterministic` as given; None follows torch's switch
+        (a Stein manifold, or one whose narrow eigenvalue window runs off the pair kernels, has no such mode and stays as it is)."""
+        if self.deterministic is None:
+            return bool(torch.are_deterministic_algorithms_enabled() and not self.use_stein_div
+                        and (self.clamps_wide or self.n < 3))
+        return bool(self.deterministic)
+
     def dist(self, x, y, squared=False, keepdim=False):  # spd.py:171-173
         shape = torch.broadcast_shapes(x.shape, y.shape)
         d = _SpdDist.apply(x.expand(shape), y.expand(shape), self.n, squared, self.wmin, self.wmax)
@@ -602,6 +716,8 @@ class SymmetricPositiveDefinite(Manifold):
         rb, re = (0, x.shape[0]) if rows is None else rows
         if not self.clamps_wide and self.n >= 3:   # (see __init__)
             return _SpdPdistGathered.apply(x, self.n, squared, self.wmin, self.wmax, int(rb), int(re))
+        if self.is_deterministic():
+            return _SpdPdistDet.apply(x, self.n, squared, self.wmin, self.wmax, int(rb), int(re), self.check_pd, self._det_ws)
         ext = B.autograd_ext()
         if ext is not None:   # the same two C-ABI calls as _SpdPdist, issued by C++ autograd nodes (csrc_torch/mm_autograd.cpp)
             try:
@@ -621,6 +737,8 @@ class SymmetricPositiveDefinite(Manifold):
         scalar loss of the pair range `rows` (all pairs by default)."""
         assert x.ndim == 3
         rb, re = (0, x.shape[0]) if rows is None else rows
+        if self.is_deterministic():
+            return _SpdPdistLossDet.apply(x, scale, target, self.n, spec, self.wmin, self.wmax, rb, re, self._det_ws)
         return _SpdPdistLoss.apply(x, scale, target, self.n, spec, self.wmin, self.wmax, rb, re)
 
     def stein_div(self, x, y, squared=False, keepdim=False):  # spd.py:183-189

@@ -89,6 +89,15 @@ _SUBSET_MAX_NODES = 2048
 _PAIR_WS_MAX = 8
 
 
+def _deterministic(man):
+    """Is `man` in the bit-deterministic mode (SymmetricPositiveDefinite(deterministic=...))?  Such a factor has no index-vector
+    kernel and no place in the mixed-manifold pair kernel (both accumulate with float atomics): its node minibatches gather
+    their rows (take_rows: distinct indices) and run the deterministic full-batch kernel, products run per-factor kernels
+    around mm_product_loss (_ProductLoss)."""
+    det = getattr(man, 'is_deterministic', None)
+    return bool(det is not None and det())
+
+
 def _pair_kernel_factor(man):
     """(kind, dim) of a factor the single mixed-manifold pair kernel (mm_product_pairs_loss) handles,
     else None."""
@@ -98,7 +107,8 @@ def _pair_kernel_factor(man):
     if isinstance(man, VectorManifold) and kind in (B.EUCLIDEAN, B.LORENTZ, B.SPHERE):
         m = getattr(man, '_m', None)
         return (kind, m) if m is not None and m <= 16 else None
-    if hasattr(man, 'wmin') and hasattr(man, 'n') and not getattr(man, 'use_stein_div', False) and getattr(man, 'clamps_wide', True):
+    if hasattr(man, 'wmin') and hasattr(man, 'n') and not getattr(man, 'use_stein_div', False) and getattr(man, 'clamps_wide', True) \
+            and not _deterministic(man):
         return (B.FACTOR_SPD, man.n) if man.n in (2, 3) else None
     return None
 
@@ -215,7 +225,8 @@ def _single_subset_factor(man):
     if isinstance(man, VectorManifold) and kind in (B.EUCLIDEAN, B.LORENTZ, B.SPHERE):
         m = getattr(man, '_m', None)
         return (kind, m) if m is not None and m <= B.lib().raw('mm_vec_max_dim')() else None
-    if hasattr(man, 'wmin') and hasattr(man, 'n') and not getattr(man, 'use_stein_div', False) and getattr(man, 'clamps_wide', True):
+    if hasattr(man, 'wmin') and hasattr(man, 'n') and not getattr(man, 'use_stein_div', False) and getattr(man, 'clamps_wide', True) \
+            and not _deterministic(man):
         return (B.FACTOR_SPD, man.n) if 2 <= man.n <= B.lib().raw('mm_spd_max_dim')() else None
     return None
 

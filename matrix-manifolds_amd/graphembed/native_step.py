@@ -75,9 +75,20 @@ def _factor_of(man):
     raise ValueError(f'no fused training step for {man}')
 
 
+def _refuse_deterministic(manifolds):
+    """mm_train_step runs the atomic pair kernels only: a manifold in the bit-deterministic mode (SymmetricPositiveDefinite
+    (deterministic=True), or deterministic=None under torch.use_deterministic_algorithms(True)) must not be stepped by it."""
+    for man in manifolds:
+        det = getattr(man, 'is_deterministic', None)
+        if det is not None and det():
+            raise ValueError(f'NativeTrainStep has no bit-deterministic mode ({man} asks for one: deterministic=True or '
+                             'torch.use_deterministic_algorithms(True)) — mm_train_step accumulates with float atomics; train '
+                             'through ManifoldEmbedding.fused_objective / BatchedObjective and the optimizers instead')
+
+
 class NativeTrainStep:
 
-    check_indices = True   # distinctness of HOST-side minibatch indices (a torch.unique per step); the range check always runs
+    check_indices = True  # distinctness of HOST-side minibatch indices (a torch.unique per step); the range check always runs
 
     def __init__(self, embedding, objective_fn, targets, optimizers, shard=None, comm=None, dense=None):
         """`dense`: the dataset's dense [n, n] matrix of squared graph distances (GraphDataset.pdists) — enables node
@@ -88,6 +99,7 @@ class NativeTrainStep:
         from graphembed.optim import RiemannianAdam, RiemannianSGD
         if not hasattr(objective_fn, 'fused_spec'):
             raise ValueError(f'{objective_fn} has no fused objective kernel')
+        _refuse_deterministic(embedding.manifolds)
         xs, scales = list(embedding.xs), list(embedding.scales)
         if not xs or not all(x.is_cuda for x in xs):
             raise ValueError('NativeTrainStep needs the embedding in GPU memory')
@@ -237,6 +249,7 @@ class NativeTrainStep:
         return True
 
     def __call__(self, indices=None, **objective_kwargs):
+        _refuse_deterministic(self.embedding.manifolds)   # (deterministic=None follows the torch switch at CALL time)
         spec = self.objective_fn.fused_spec(**objective_kwargs)
         d = self._desc
         if indices is not None:

@@ -458,6 +458,9 @@ CASES = {
     'c2_facebook_lorentz11_step_f32_fused': lambda: step_case([M.Lorentz(11)], 4039, torch.float32, fused=True),
     'c2_facebook_lorentz11_step_f32_fused_graph': lambda: step_case([M.Lorentz(11)], 4039, torch.float32, fused=True, graph=True),
     'c3_grqc_spd3_n5000_f32': lambda: pdist_case(M.SymmetricPositiveDefinite(3), 5000, torch.float32),
+    # the bit-deterministic mode (csrc/spd_det.hpp) beside its atomic twins: measure each pair in ONE run on one box
+    # (profiles/spd_deterministic.md)
+    'c3_grqc_spd3_n5000_f32_deterministic': lambda: pdist_case(M.SymmetricPositiveDefinite(3, deterministic=True), 5000, torch.float32),
     'c3_grqc_spd3_n4158_f32': lambda: pdist_case(M.SymmetricPositiveDefinite(3), 4158, torch.float32),
     'c3_grqc_spd3_n5000_f64': lambda: pdist_case(M.SymmetricPositiveDefinite(3), 5000, torch.float64),
     # "mid-training" spread: ||log X|| = 0.35 -> pair distances ~0.5 (targets are normalised to max 1)
@@ -483,10 +486,12 @@ CASES = {
     'c4_csphd_product_step_f32_graph': lambda: step_case([M.Lorentz(6), M.Sphere(6), M.SymmetricPositiveDefinite(2)], 1025, torch.float32, graph=True),
     'c4_csphd_product_step_f64': lambda: step_case([M.Lorentz(6), M.Sphere(6), M.SymmetricPositiveDefinite(2)], 1025, torch.float64),
     'c5_wormnet_spd4_n2274_f32': lambda: pdist_case(M.SymmetricPositiveDefinite(4), 2274, torch.float32),
+    'c5_wormnet_spd4_n2274_f32_deterministic': lambda: pdist_case(M.SymmetricPositiveDefinite(4, deterministic=True), 2274, torch.float32),
     'c5_wormnet_spd4_n16384_f32': lambda: pdist_case(M.SymmetricPositiveDefinite(4), 16384, torch.float32),
     'c3_spd3_step_n5000_f32': lambda: step_case([M.SymmetricPositiveDefinite(3)], 5000, torch.float32),
     'c3_spd3_step_n5000_f32_fused': lambda: step_case([M.SymmetricPositiveDefinite(3)], 5000, torch.float32, fused=True),
     'c3_spd3_step_n5000_f32_fused_graph': lambda: step_case([M.SymmetricPositiveDefinite(3)], 5000, torch.float32, fused=True, graph=True),
+    'c3_spd3_step_n5000_f32_fused_graph_deterministic': lambda: step_case([M.SymmetricPositiveDefinite(3, deterministic=True)], 5000, torch.float32, fused=True, graph=True),
     'c3_spd3_step_n5000_f32_graph': lambda: step_case([M.SymmetricPositiveDefinite(3)], 5000, torch.float32, graph=True),
     'c3_spd3_step_n5000_f32_native_graph': lambda: native_case([M.SymmetricPositiveDefinite(3)], 5000, torch.float32),
     'c3_spd3_step_n5000_f64_native_graph': lambda: native_case([M.SymmetricPositiveDefinite(3)], 5000, torch.float64),
