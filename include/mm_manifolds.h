@@ -357,6 +357,55 @@ int mm_vec_pdist_loss_subset(int dtype, int kind, int loss_kind, const void* x, 
                              int64_t n_total, int m, const int64_t* idx, int64_t bs, int64_t row_begin, int64_t row_end,
                              double alpha, double eps, int terms, const double* loss_params, void* loss_out, void* grad_x,
                              void* ws, mm_stream_t stream);
+
+/* ---- vector manifolds: the BIT-DETERMINISTIC mode of the three entries above (csrc/vec_det.hpp) ----
+ * mm_vec_pdist_bwd, mm_vec_pdist_loss and mm_vec_pdist_loss_subset accumulate with float atomics in every one of their forms
+ * (symmetric VALU, matrix cores, ordered pairs): two runs on the same inputs differ in the last bits.  The _det entries compute
+ * the same quantities without any atomic — a lane owns a COLUMN node j and visits every i != j (both orders of a pair, the
+ * per-pair arithmetic of the ordered atomic kernel), its sums of one chunk of rows leave with plain stores and a per-node
+ * kernel adds a node's chunk records in chunk order — and return the same bits for the same (dtype, kind, n, m, row range,
+ * inputs) on every call: eagerly or replayed from a graph, whatever det_ws held before, whatever MM_VEC_* / MM_GRAM_* say
+ * (no environment switch selects or alters these kernels).
+ *
+ * Geometry (host only, no GPU work): the n rows are cut into `chunks` chunks of `rows_per_chunk` rows (a multiple of 8),
+ * (chunks - 1) rows_per_chunk < n <= chunks rows_per_chunk; both — and with them every order of summation — are a pure
+ * function of (dtype, kind, n, m): never of the row range, the device, an occupancy query or the environment.  The grid is
+ * sized towards 1024 workgroups of 256 columns, so chunks falls as n grows and the scratch stays bounded:
+ *   mm_vec_pdist_det_ws_bytes = chunks E n sizeof(T)       the slab [chunks][E][n], E = m (+ 1 for MM_EUCLIDEAN: the weights)
+ *                             + 2 groups chunks sizeof(T)  one {loss, dloss/dsoftplus} slot per workgroup, groups = ceil(n / 256)
+ *   (each part rounded up to 64 bytes), and the slab is at most max(E n sizeof(T), B) with B = 64 MiB.
+ * mm_vec_pdist_det_geometry: MM_ERR_ARG for a dtype other than MM_F32 / MM_F64, an unknown kind, n < 1, n > 2^22, m outside
+ * 1 ... mm_vec_max_dim() or null outputs.
+ *
+ * mm_vec_pdist_bwd_det / mm_vec_pdist_loss_det / mm_vec_pdist_loss_subset_det take the arguments of the atomic entries with
+ * `ws` REPLACED by `det_ws` (mm_vec_pdist_det_ws_bytes(dtype, kind, n, m) bytes; the minibatch entry: of (dtype, kind, bs, m) —
+ * the slab is addressed by batch position, with the geometry of a full batch of bs points).  det_ws may hold anything on
+ * entry: every record the per-node kernel reads is written by the same call.  Capture-safe, no allocation, no
+ * synchronisation.  Every kind, every m <= mm_vec_max_dim(), fp32 and fp64; squared and !squared; MM_LOSS_STRESS and
+ * MM_LOSS_QUOTIENT.  The minibatch entry reads the target of batch pair (a, b), a < b by POSITION, at dense[idx[a]][idx[b]]
+ * (no symmetry assumed), clamps node ids into the table, and OVERWRITES grad_x [n_total, m]: rows idx[.] (distinct) with the
+ * gradient, every other row with +0.  On the gathered rows x[idx] with the targets dense[idx[a]][idx[b]] the full-batch entry
+ * returns the same bits.
+ * MM_ERR_ARG: null x / det_ws / grad_x (/ loss_out), null g / target / dense / idx with a non-empty pair range, a row range
+ * outside [0, n], the quotient loss with terms & 3 == 0; MM_ERR_UNSUPPORTED: m > mm_vec_max_dim(), n (bs) > 2^22, another loss
+ * kind.  All of them before anything touches the GPU.  An empty row range, or bs <= 1: all-zero grad_x, zero loss record.
+ * The loss record is summed per workgroup in a fixed order and over the workgroups' slots in fp64 (lane t of one wavefront
+ * the slots t, t + 64, ... in index order, the 64 lane sums through a fixed butterfly).  Offsets are 64-bit as in the ordered
+ * atomic kernel (not exercised past 32 bits). */
+size_t mm_vec_pdist_det_ws_bytes(int dtype, int kind, int64_t n, int m);
+int mm_vec_pdist_det_geometry(int dtype, int kind, int64_t n, int m, int64_t* chunks, int64_t* rows_per_chunk);
+int mm_vec_pdist_bwd_det(int dtype, int kind, const void* x, const void* g, int64_t n, int m,
+                         int64_t row_begin, int64_t row_end, int squared, void* grad_x, void* det_ws,
+                         mm_stream_t stream);
+int mm_vec_pdist_loss_det(int dtype, int kind, int loss_kind, const void* x, const void* target,
+                          const void* scale_raw, int64_t n, int m, int64_t row_begin, int64_t row_end,
+                          double alpha, double eps, int terms, const double* loss_params, void* loss_out, void* grad_x,
+                          void* det_ws, mm_stream_t stream);
+int mm_vec_pdist_loss_subset_det(int dtype, int kind, int loss_kind, const void* x, const void* dense, const void* scale_raw,
+                                 int64_t n_total, int m, const int64_t* idx, int64_t bs, int64_t row_begin, int64_t row_end,
+                                 double alpha, double eps, int terms, const double* loss_params, void* loss_out, void* grad_x,
+                                 void* det_ws, mm_stream_t stream);
+
 /* Element-wise dist over cnt pairs (x[k],y[k]).  out may be NULL (backward only);
  * grad_x/grad_y may both be NULL (forward only), else g [cnt] is required. */
 int mm_vec_dist(int dtype, int kind, const void* x, const void* y, const void* g, int64_t cnt, int m,

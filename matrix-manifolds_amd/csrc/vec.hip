@@ -22,6 +22,7 @@
 #include "smallmat.hpp"
 #include "loss.hpp"
 #include "vecfn.hpp"
+#include "vec_pair.hpp"
 #include "vec_step.hpp"
 #include "vec_rules.hpp"
 #include "spd_ws.hpp"
@@ -34,30 +35,7 @@ constexpr int kVecMaxDim = 64;
 constexpr int kVecSubMaxRows = 64;   // most rows per workgroup of the node-minibatch launch (their points sit in LDS)
 __host__ __device__ inline int64_t vpair_off(int64_t n, int64_t row) { return row * (2 * n - row - 1) / 2; }
 
-// q for one pair from register/scalar operands
-template <typename T, int KIND, int MP, typename TI>
-__device__ __forceinline__ T pair_q(const TI (&xi)[MP], const T (&xj)[MP]) {
-  using N = Num<T>;
-  T q = T(0);
-  if (KIND == MM_EUCLIDEAN) {
-#pragma unroll
-    for (int k = 0; k < MP; ++k) { const T df = xj[k] - xi[k]; q = N::fma(df, df, q); }
-  } else if (KIND == MM_LORENTZ) {
-#pragma unroll
-    for (int k = 1; k < MP; ++k) q = N::fma(xi[k], xj[k], q);
-    q = N::fma(xi[0], xj[0], -q);  // -( -x0 y0 + sum x_k y_k )
-  } else {
-#pragma unroll
-    for (int k = 0; k < MP; ++k) q = N::fma(xi[k], xj[k], q);
-  }
-  return q;
-}
-
-template <typename T, int MP>
-__device__ __forceinline__ void load_point(const T* __restrict__ x, int64_t idx, int m, T (&r)[MP]) {
-#pragma unroll
-  for (int k = 0; k < MP; ++k) r[k] = (k < m) ? x[idx * m + k] : T(0);
-}
+// (pair_q, load_point: vec_pair.hpp — shared with the bit-deterministic kernels of vec_det.hpp)
 
 // ------------------------------------------------------------------ forward
 // (rows per tile: a launch argument — 32 for a launch that fills the device, fewer for small ones: tree40's 40 rows were ONE

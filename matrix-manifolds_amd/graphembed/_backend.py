@@ -117,6 +117,13 @@ SIGNATURES = {
     'mm_vec_pdist_bwd': (_i, [_i, _i, _vp, _vp, _i64, _i, _i64, _i64, _i, _vp, _vp, _vp]),
     'mm_vec_pdist_bwd_gram': (_i, [_i, _i, _vp, _vp, _i64, _i, _i64, _i64, _i, _vp, _vp]),
     'mm_vec_pdist_loss': (_i, [_i, _i, _i, _vp, _vp, _vp, _i64, _i, _i64, _i64, _dbl, _dbl, _i, _vp, _vp, _vp, _vp, _vp]),
+    # the bit-deterministic mode (csrc/vec_det.hpp): the atomic entries' arguments with `ws` replaced by `det_ws`
+    'mm_vec_pdist_det_ws_bytes': (_sz, [_i, _i, _i64, _i]),
+    'mm_vec_pdist_det_geometry': (_i, [_i, _i, _i64, _i, _c.POINTER(_i64), _c.POINTER(_i64)]),
+    'mm_vec_pdist_bwd_det': (_i, [_i, _i, _vp, _vp, _i64, _i, _i64, _i64, _i, _vp, _vp, _vp]),
+    'mm_vec_pdist_loss_det': (_i, [_i, _i, _i, _vp, _vp, _vp, _i64, _i, _i64, _i64, _dbl, _dbl, _i, _vp, _vp, _vp, _vp, _vp]),
+    'mm_vec_pdist_loss_subset_det': (_i, [_i, _i, _i, _vp, _vp, _vp, _i64, _i, _vp, _i64, _i64, _i64, _dbl, _dbl, _i, _vp, _vp,
+                                           _vp, _vp, _vp]),
     'mm_vec_dist': (_i, [_i, _i, _vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp]),
     'mm_vec_map': (_i, [_i, _i, _i, _vp, _vp, _vp, _i64, _i, _vp, _vp]),
     'mm_vec_norm': (_i, [_i, _i, _vp, _i64, _i, _i, _vp, _vp]),

@@ -24,9 +24,13 @@ def _shape_name(kind, shape):
 class Euclidean(VectorManifold):
     _kind = B.EUCLIDEAN
 
-    def __init__(self, *shape):
+    def __init__(self, *shape, deterministic=None):
+        """`deterministic`: True — the gradients of `pdist` and the fused objective `pdist_loss` come from the bit-deterministic
+        kernels (csrc/vec_det.hpp: no float atomics, the same bits on every call); False — never; None (default) — follow
+        torch.are_deterministic_algorithms_enabled() at call time."""
         if not shape:
             raise ValueError('Need shape parameters.')
+        self.deterministic = deterministic
         self.shape = shape
         self.dims = tuple(range(-len(shape), 0))   # the point dimensions, for reductions
         self._name = _shape_name('Euclidean', shape)

@@ -17,8 +17,12 @@ class Lorentz(VectorManifold):
     _kind = B.LORENTZ
     use_gram = True
 
-    def __init__(self, n):
+    def __init__(self, n, deterministic=None):
+        """`deterministic`: True — the gradients of `pdist` and the fused objective `pdist_loss` come from the bit-deterministic
+        kernels (csrc/vec_det.hpp: no float atomics, the same bits on every call); False — never; None (default) — follow
+        torch.are_deterministic_algorithms_enabled() at call time."""
         self.n = n
+        self.deterministic = deterministic
         self.shape = (n, )
         self.sphere = Sphere(self.n - 1)
 

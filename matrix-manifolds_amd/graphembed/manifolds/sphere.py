@@ -12,9 +12,13 @@ class Sphere(VectorManifold):
     _kind = B.SPHERE
     use_gram = True
 
-    def __init__(self, *shape):
+    def __init__(self, *shape, deterministic=None):
+        """`deterministic`: True — the gradients of `pdist` and the fused objective `pdist_loss` come from the bit-deterministic
+        kernels (csrc/vec_det.hpp: no float atomics, the same bits on every call); False — never; None (default) — follow
+        torch.are_deterministic_algorithms_enabled() at call time."""
         if len(shape) == 0:
             raise ValueError('Need shape parameters.')
+        self.deterministic = deterministic
         self.shape = shape
         self._name = _shape_name('Sphere', shape)
         self.dims = tuple(np.arange(-len(shape), 0))

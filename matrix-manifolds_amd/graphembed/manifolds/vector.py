@@ -112,6 +112,108 @@ class _VecPdistLoss(torch.autograd.Function):
         return gx, gs, None, None, None, None, None, None
 
 
+def _det_ws(cache, x, kind, m, n):
+    """The scratch of the bit-deterministic pair kernels (mm_vec_pdist_det_ws_bytes: chunk records and loss slots) for a launch of
+    `n` points, kept in `cache` per (dtype, device, n): a captured step refers to it and does not allocate.  It may hold anything
+    between calls."""
+    key = (x.dtype, x.device, n)
+    ws = cache.get(key)
+    if ws is None:
+        ws = torch.empty(B.lib().raw('mm_vec_pdist_det_ws_bytes')(B.dtype_code(x), kind, n, m), dtype=torch.uint8, device=x.device)
+        cache[key] = ws
+    return ws
+
+
+class _VecPdistDet(torch.autograd.Function):
+    """_VecPdist with the backward of the bit-deterministic mode (mm_vec_pdist_bwd_det: no float atomics; the forward kernels
+    have none anyway).  Hosted in Python: the C++ autograd node issues the atomic pair of calls only."""
+
+    @staticmethod
+    def forward(ctx, x, kind, m, squared, row_begin, row_end, use_gram, cache):
+        out = _VecPdist.forward(ctx, x, kind, m, squared, row_begin, row_end, use_gram)
+        ctx.cache = cache
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        xc, = ctx.saved_tensors
+        kind, m, squared, row_begin, row_end, shape = ctx.args
+        if ctx.empty:
+            return (torch.zeros(shape, dtype=xc.dtype, device=xc.device), ) + (None, ) * 7
+        g = g.contiguous()
+        n = xc.shape[0]
+        with B.on_device(xc.device):
+            grad = torch.empty_like(xc)
+            B.lib().call('mm_vec_pdist_bwd_det', B.dtype_code(xc), kind, B.ptr(xc), B.ptr(g), n, m, row_begin, row_end,
+                         int(squared), B.ptr(grad), B.ptr(_det_ws(ctx.cache, xc, kind, m, n)), B.stream_of(xc))
+        return (grad.reshape(shape), ) + (None, ) * 7
+
+
+class _VecPdistLossDet(torch.autograd.Function):
+    """_VecPdistLoss in the bit-deterministic mode (mm_vec_pdist_loss_det): the same loss record and gradients without a float
+    atomic — the same bits on every call."""
+
+    @staticmethod
+    def forward(ctx, x, scale, target, kind, m, spec, row_begin, row_end, cache):
+        B.require_gpu(x, target)
+        n = x.shape[0]
+        xc = x.detach().reshape(n, m).contiguous()
+        lkind, alpha, eps, terms = spec[:4]
+        dyn = spec[4] if len(spec) > 4 else None  # device {alpha, eps} (QuotientLoss.on_device)
+        tc = target.detach().to(xc.dtype).contiguous()
+        npairs = B.pair_offset(n, row_end) - B.pair_offset(n, row_begin)
+        if tc.numel() != npairs:
+            raise ValueError(f'target has {tc.numel()} entries, the pair range has {npairs}')
+        sc = None if scale is None else scale.detach().to(xc.dtype).reshape(1).contiguous()
+        with B.on_device(xc.device):
+            out = torch.empty(2, dtype=xc.dtype, device=xc.device)
+            grad = torch.empty_like(xc)
+            B.lib().call('mm_vec_pdist_loss_det', B.dtype_code(xc), kind, B.LOSS_STRESS if lkind == 'stress' else B.LOSS_QUOTIENT,
+                         B.ptr(xc), B.ptr(tc), B.ptr(sc), n, m, row_begin, row_end, alpha, eps, terms, B.dyn_ptr(dyn, xc),
+                         B.ptr(out), B.ptr(grad), B.ptr(_det_ws(cache, xc, kind, m, n)), B.stream_of(xc))
+        ctx.grad_x = grad.reshape(x.shape)
+        ctx.grad_s = None if scale is None else out[1].reshape(scale.shape).to(scale.dtype)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, up):
+        gx, gs = B.take_grads(ctx, up, 'grad_x', 'grad_s')
+        return (gx, gs) + (None, ) * 7
+
+
+class _VecSubsetLossDet(torch.autograd.Function):
+    """The fused objective of the node minibatch `idx` of the full table `x` in the bit-deterministic mode
+    (mm_vec_pdist_loss_subset_det): targets dense[idx[a], idx[b]], a < b by position; the gradient comes back full-size, rows
+    outside the batch +0.  The indices must be distinct."""
+
+    @staticmethod
+    def forward(ctx, x, scale, idx, dense, kind, m, spec, row_begin, row_end, cache):
+        B.require_gpu(x, dense)
+        n_total, bs = x.shape[0], idx.numel()
+        lkind, alpha, eps, terms = spec[:4]
+        dyn = spec[4] if len(spec) > 4 else None
+        if dense.dtype != x.dtype or not dense.is_contiguous() or dense.shape != (n_total, n_total):
+            raise ValueError('dense targets must be a contiguous [n, n] matrix of the embedding\'s dtype')
+        with B.on_device(x.device):
+            xc = x.detach().reshape(n_total, m).contiguous()
+            sc = None if scale is None else scale.detach().to(xc.dtype).reshape(1).contiguous()
+            ic = idx.to(device=x.device, dtype=torch.int64).contiguous()
+            out = torch.empty(2, dtype=xc.dtype, device=xc.device)
+            grad = torch.empty_like(xc)
+            B.lib().call('mm_vec_pdist_loss_subset_det', B.dtype_code(xc), kind,
+                         B.LOSS_STRESS if lkind == 'stress' else B.LOSS_QUOTIENT, B.ptr(xc), B.ptr(dense), B.ptr(sc), n_total, m,
+                         B.ptr(ic), bs, row_begin, row_end, alpha, eps, terms, B.dyn_ptr(dyn, xc), B.ptr(out), B.ptr(grad),
+                         B.ptr(_det_ws(cache, xc, kind, m, bs)), B.stream_of(xc))
+        ctx.grad_x = grad.reshape(x.shape)
+        ctx.grad_s = None if scale is None else out[1].reshape(scale.shape).to(scale.dtype)
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, up):
+        gx, gs = B.take_grads(ctx, up, 'grad_x', 'grad_s')
+        return (gx, gs) + (None, ) * 8
+
+
 class _VecDist(torch.autograd.Function):
 
     @staticmethod
@@ -145,6 +247,22 @@ class VectorManifold(Manifold):
 
     _kind = None
     use_gram = False  # forward pdist through the MFMA Gram kernel (inner-product manifolds)
+    deterministic = None  # the constructors' keyword: see is_deterministic
+
+    def is_deterministic(self):
+        """Do `pdist` / `pdist_loss` take the bit-deterministic kernels (csrc/vec_det.hpp) now?  `deterministic` as given; None
+        follows torch's switch at call time."""
+        if self.deterministic is None:
+            return bool(torch.are_deterministic_algorithms_enabled())
+        return bool(self.deterministic)
+
+    @property
+    def _det_cache(self):
+        """scratch of the deterministic kernels per (dtype, device, n): see _det_ws"""
+        cache = self.__dict__.get('_det_ws')
+        if cache is None:
+            cache = self.__dict__['_det_ws'] = {}
+        return cache
 
     @property
     def _m(self):
@@ -264,6 +382,8 @@ class VectorManifold(Manifold):
         pair-list slice of one shard (graphembed.parallel)."""
         assert x.ndim == self.ndim + 1
         rb, re = (0, x.shape[0]) if rows is None else rows
+        if self.is_deterministic():   # (the C++ autograd node hosts the atomic pair of calls only)
+            return _VecPdistDet.apply(x, self._kind, self._m, squared, int(rb), int(re), self.use_gram, self._det_cache)
         ext = B.autograd_ext()
         if ext is not None:   # the same C-ABI calls as _VecPdist, issued by C++ autograd nodes (csrc_torch/mm_autograd.cpp)
             fwd_gram, bwd_gram = _pdist_forms(self._kind, self._m, x.shape[0], x.dtype == torch.float32, bool(squared),
@@ -281,7 +401,21 @@ class VectorManifold(Manifold):
         one pass; `spec` comes from `objective_fn.fused_spec(epoch=, alpha=)`."""
         assert x.ndim == self.ndim + 1
         rb, re = (0, x.shape[0]) if rows is None else rows
+        if self.is_deterministic():
+            return _VecPdistLossDet.apply(x, scale, target, self._kind, self._m, spec, rb, re, self._det_cache)
         return _VecPdistLoss.apply(x, scale, target, self._kind, self._m, spec, rb, re)
+
+    def pdist_loss_subset(self, x, scale, idx, dense, spec, rows=None, cache=None):
+        """`pdist_loss` for the node minibatch `idx` (distinct) of the full table `x` with the targets dense[idx[a], idx[b]],
+        inside the bit-deterministic pair kernel (mm_vec_pdist_loss_subset_det); None when the manifold is not in that mode (the
+        atomic in-kernel routes of graphembed.modules serve it) or the tensors are not eligible — the caller then gathers."""
+        if not self.is_deterministic():
+            return None
+        if not (x.is_cuda and dense.is_cuda and x.dtype in (torch.float32, torch.float64) and x.ndim == self.ndim + 1
+                and 1 <= self._m <= B.lib().raw('mm_vec_max_dim')() and idx.numel() <= (1 << 22)):
+            return None
+        rb, re = (0, idx.numel()) if rows is None else rows
+        return _VecSubsetLossDet.apply(x, scale, idx, dense, self._kind, self._m, spec, int(rb), int(re), self._det_cache)
 
 
 def _vec_radam(kind, m, x, egrad, exp_avg, exp_avg_sq, step, ticket, lr, betas, nc, eps, max_grad_norm, exact,

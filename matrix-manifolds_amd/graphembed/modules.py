@@ -90,10 +90,11 @@ _PAIR_WS_MAX = 8
 
 
 def _deterministic(man):
-    """Is `man` in the bit-deterministic mode (SymmetricPositiveDefinite(deterministic=...))?  Such a factor has no index-vector
-    kernel and no place in the mixed-manifold pair kernel (both accumulate with float atomics): its node minibatches gather
-    their rows (take_rows: distinct indices) and run the deterministic full-batch kernel, products run per-factor kernels
-    around mm_product_loss (_ProductLoss)."""
+    """Is `man` in the bit-deterministic mode (SymmetricPositiveDefinite / Euclidean / Lorentz / Sphere(deterministic=...))?
+    Such a factor has no place in the atomic index-vector kernels or in the mixed-manifold pair kernel (they accumulate with
+    float atomics).  An SPD factor's node minibatches gather their rows (take_rows: distinct indices) and run the deterministic
+    full-batch kernel; a vector factor's go through its own deterministic index-vector kernel (VectorManifold.pdist_loss_subset);
+    products run per-factor kernels around mm_product_loss (_ProductLoss)."""
     det = getattr(man, 'is_deterministic', None)
     return bool(det is not None and det())
 
@@ -106,7 +107,7 @@ def _pair_kernel_factor(man):
     kind = getattr(man, '_kind', None)
     if isinstance(man, VectorManifold) and kind in (B.EUCLIDEAN, B.LORENTZ, B.SPHERE):
         m = getattr(man, '_m', None)
-        return (kind, m) if m is not None and m <= 16 else None
+        return (kind, m) if m is not None and m <= 16 and not _deterministic(man) else None
     if hasattr(man, 'wmin') and hasattr(man, 'n') and not getattr(man, 'use_stein_div', False) and getattr(man, 'clamps_wide', True) \
             and not _deterministic(man):
         return (B.FACTOR_SPD, man.n) if man.n in (2, 3) else None
@@ -224,7 +225,7 @@ def _single_subset_factor(man):
     kind = getattr(man, '_kind', None)
     if isinstance(man, VectorManifold) and kind in (B.EUCLIDEAN, B.LORENTZ, B.SPHERE):
         m = getattr(man, '_m', None)
-        return (kind, m) if m is not None and m <= B.lib().raw('mm_vec_max_dim')() else None
+        return (kind, m) if m is not None and m <= B.lib().raw('mm_vec_max_dim')() and not _deterministic(man) else None
     if hasattr(man, 'wmin') and hasattr(man, 'n') and not getattr(man, 'use_stein_div', False) and getattr(man, 'clamps_wide', True) \
             and not _deterministic(man):
         return (B.FACTOR_SPD, man.n) if 2 <= man.n <= B.lib().raw('mm_spd_max_dim')() else None
@@ -475,7 +476,8 @@ class ManifoldEmbedding(torch.nn.Module):
                 factor = _single_subset_factor(self.manifolds[0])
                 if factor is not None:
                     return _SingleSubsetLoss.apply(spec, rows, self.manifolds[0], factor, self._pair_ws, i, dense, pts[0], scales[0])
-                # Grassmann, SO(n): their own pair kernels with the index vector (mm_grass_pdist_loss_subset, mm_so_pdist_loss_subset)
+                # Grassmann, SO(n), a deterministic vector factor: their own pair kernels with the index vector
+                # (mm_grass_pdist_loss_subset, mm_so_pdist_loss_subset, mm_vec_pdist_loss_subset_det)
                 subset = getattr(self.manifolds[0], 'pdist_loss_subset', None)
                 if subset is not None:
                     loss = subset(pts[0], scales[0], i, dense, spec, rows=rows, cache=self._pair_ws)

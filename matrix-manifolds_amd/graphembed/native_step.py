@@ -76,8 +76,8 @@ def _factor_of(man):
 
 
 def _refuse_deterministic(manifolds):
-    """mm_train_step runs the atomic pair kernels only: a manifold in the bit-deterministic mode (SymmetricPositiveDefinite
-    (deterministic=True), or deterministic=None under torch.use_deterministic_algorithms(True)) must not be stepped by it."""
+    """mm_train_step runs the atomic pair kernels only: a manifold in the bit-deterministic mode (SymmetricPositiveDefinite,
+    Euclidean, Lorentz or Sphere with deterministic=True, or deterministic=None under torch.use_deterministic_algorithms(True)) must not be stepped by it."""
     for man in manifolds:
         det = getattr(man, 'is_deterministic', None)
         if det is not None and det():

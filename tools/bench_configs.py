@@ -454,6 +454,11 @@ CASES = {
     'c2_facebook_lorentz11_f32_valu': lambda: pdist_case(_valu(M.Lorentz(11)), 4039, torch.float32),
     'c2_facebook_lorentz11_f64_gram': lambda: pdist_case(M.Lorentz(11), 4039, torch.float64),
     'c2_facebook_lorentz11_f64_valu': lambda: pdist_case(_valu(M.Lorentz(11)), 4039, torch.float64),
+    # the bit-deterministic mode of the vector manifolds (csrc/vec_det.hpp) beside its atomic twins: measure each pair in ONE run on
+    # one box (profiles/vec_deterministic.md)
+    'c2_facebook_lorentz11_f32_deterministic': lambda: pdist_case(M.Lorentz(11, deterministic=True), 4039, torch.float32),
+    'c2_facebook_lorentz11_f64_deterministic': lambda: pdist_case(M.Lorentz(11, deterministic=True), 4039, torch.float64),
+    'c2_facebook_lorentz11_step_f32_fused_graph_deterministic': lambda: step_case([M.Lorentz(11, deterministic=True)], 4039, torch.float32, fused=True, graph=True),
     'c2_facebook_lorentz11_step_f32': lambda: step_case([M.Lorentz(11)], 4039, torch.float32),
     'c2_facebook_lorentz11_step_f32_fused': lambda: step_case([M.Lorentz(11)], 4039, torch.float32, fused=True),
     'c2_facebook_lorentz11_step_f32_fused_graph': lambda: step_case([M.Lorentz(11)], 4039, torch.float32, fused=True, graph=True),
@@ -517,6 +522,14 @@ CASES = {
     'lorentz24_minibatch512_step_n4039_f32_native_graph': lambda: native_minibatch_case([M.Lorentz(24)], 4039, 512, torch.float32),
     'sphere6_n5000_f32': lambda: pdist_case(M.Sphere(6), 5000, torch.float32),
     'euclidean10_n5000_f32': lambda: pdist_case(M.Euclidean(10), 5000, torch.float32),
+    'sphere6_n5000_f32_deterministic': lambda: pdist_case(M.Sphere(6, deterministic=True), 5000, torch.float32),
+    'euclidean10_n5000_f32_deterministic': lambda: pdist_case(M.Euclidean(10, deterministic=True), 5000, torch.float32),
+    # Lorentz(24) at batch 512 of 4039, replayed: the index vector inside the pair kernel | `gather`: rows and targets gathered, the
+    # full-batch kernel on them, the gradient rows scattered back — in either mode
+    'lorentz24_minibatch512_step_n4039_f32_graph': lambda: minibatch_case([M.Lorentz(24)], 4039, 512, torch.float32, graph=True),
+    'lorentz24_minibatch512_step_n4039_f32_graph_gather': lambda: minibatch_case([M.Lorentz(24)], 4039, 512, torch.float32, graph=True, gather=True),
+    'lorentz24_minibatch512_step_n4039_f32_graph_deterministic': lambda: minibatch_case([M.Lorentz(24, deterministic=True)], 4039, 512, torch.float32, graph=True),
+    'lorentz24_minibatch512_step_n4039_f32_graph_deterministic_gather': lambda: minibatch_case([M.Lorentz(24, deterministic=True)], 4039, 512, torch.float32, graph=True, gather=True),
     'grassmann52_n2000_f32': lambda: pdist_case(M.Grassmann(5, 2), 2000, torch.float32),
     # Grassmann training steps: per-factor objective (pdist forward, loss, pdist backward) | one pair kernel (mm_grass_pdist_loss);
     # the optimizer update is one launch in all of them (mm_mat_rsgd_step)
@@ -628,9 +641,10 @@ def unrolled_case(mans, n, dtype, unroll):
     return {'n': n, 'pairs': P, 'dtype': str(dtype).split('.')[-1], 'step_us': t, 'pairs_per_s': P / (t * 1e-6)}
 
 
-def minibatch_case(mans, n, bs, dtype, graph=False, adam=False):
+def minibatch_case(mans, n, bs, dtype, graph=False, adam=False, gather=False):
     """node-minibatch training step as train.py:198-222 runs it (batch_size=512 in the paper grid): targets of the
-    induced sub-graph from the dense matrix, embedding rows gathered, fused loss, scatter-add backward, RSGD"""
+    induced sub-graph from the dense matrix, embedding rows gathered, fused loss, scatter-add backward, RSGD; `gather`: keep
+    the batch out of the pair kernels' index-vector forms (rows and targets gathered, gradient rows scattered back)"""
     from graphembed.data import GraphDataset
     from graphembed.modules import BatchedObjective
     torch.manual_seed(0)
@@ -638,6 +652,7 @@ def minibatch_case(mans, n, bs, dtype, graph=False, adam=False):
     try:
         with torch.device('cuda'):
             emb = ManifoldEmbedding(n, mans)
+            emb.pair_kernel = not gather
             ds = GraphDataset(torch.rand(n * (n - 1) // 2) * 0.99 + 0.01)
     finally:
         torch.set_default_dtype(torch.float32)
