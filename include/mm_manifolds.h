@@ -490,7 +490,8 @@ int mm_mat_map(int dtype, int kind, int op, const void* x, const void* u, int64_
  * reference yields NaN, is replaced by its finite limit.) */
 int mm_grass_dist(int dtype, const void* x, const void* y, const void* g, int64_t cnt, int N, int p,
                   int squared, void* out, void* grad_x, void* grad_y, mm_stream_t stream);
-/* Manifold.pdist default (base.py:59-63) with Grassmann.dist, row-range layout as above. */
+/* Manifold.pdist default (base.py:59-63) with Grassmann.dist, row-range layout as above.  The backward OVERWRITES grad_x [n,N,p];
+ * its ws: mm_grass_pdist_ws_bytes(dtype, n, N, p) bytes, may hold anything: cleared by the call. */
 size_t mm_grass_pdist_ws_bytes(int dtype, int64_t n, int N, int p);
 int mm_grass_pdist_fwd(int dtype, const void* x, int64_t n, int N, int p, int64_t row_begin,
                        int64_t row_end, int squared, void* out, mm_stream_t stream);

@@ -19,6 +19,7 @@
 
 #include <climits>
 
+#include "clear.hpp"
 #include "grass_loss.hpp"
 
 namespace mm {
@@ -69,7 +70,7 @@ int mm_grass_pdist_loss(int dtype, int loss_kind, const void* x, const void* tar
   const bool pairs = mm_pair_offset(n, row_end) > mm_pair_offset(n, row_begin);
   if (!target && pairs) return MM_ERR_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  hipError_t e = hipMemsetAsync(ws, 0, mm_grass_pdist_loss_ws_bytes(dtype, n, N, p), st);
+  hipError_t e = clear_async(ws, mm_grass_pdist_loss_ws_bytes(dtype, n, N, p), st);   // (a kernel: clear.hpp says why)
   if (e != hipSuccess) return int(e);
   MMM_DISPATCH_T(dtype, MMM_DISPATCH_NP_P(N, p, {
     T* acc = static_cast<T*>(ws);

@@ -1,8 +1,8 @@
 // The fused Grassmann objective for a NODE MINIBATCH (mm_grass_pdist_loss_subset): the pair kernel of grass_loss.hpp with SUB —
 // the points of the step are rows idx[0..bs) of the full table, the target of batch pair (a, b) is dense[idx[a]][idx[b]], and
-// the sums land in accumulators addressed by node, acc [N*p][n_total].  A step is the memset of the workspace, the pair kernel
+// the sums land in accumulators addressed by node, acc [N*p][n_total].  A step is the clear kernel over the workspace (clear.hpp), the pair kernel
 // over the batch's tiles and the full-batch finalize launch over n_total, which writes the whole dense gradient: rows outside
-// the batch come out as the +0 the memset left.  No gather, no scatter-add, no zero fill.  The price is the column side's
+// the batch come out as the +0 the clear kernel left.  No gather, no scatter-add, no zero fill.  The price is the column side's
 // atomics, which are scattered over the node ids instead of 64 consecutive addresses (one per value and tile, as before).
 // A translation unit of its own, so that the library's build stays parallel.
 //
@@ -13,6 +13,7 @@
 
 #include <climits>
 
+#include "clear.hpp"
 #include "grass_loss.hpp"
 
 namespace mm {
@@ -67,7 +68,7 @@ int mm_grass_pdist_loss_subset(int dtype, int loss_kind, const void* x, const vo
   const bool pairs = bs >= 2 && mm_pair_offset(bs, row_end) > mm_pair_offset(bs, row_begin);
   if (pairs && (!dense || !idx)) return MM_ERR_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  hipError_t e = hipMemsetAsync(ws, 0, mm_grass_pdist_loss_ws_bytes(dtype, n_total, N, p), st);
+  hipError_t e = clear_async(ws, mm_grass_pdist_loss_ws_bytes(dtype, n_total, N, p), st);   // (a kernel: clear.hpp says why)
   if (e != hipSuccess) return int(e);
   MMM_DISPATCH_T(dtype, MMM_DISPATCH_NP_P(N, p, {
     T* acc = static_cast<T*>(ws);

@@ -16,6 +16,7 @@
 #include "prof.hpp"
 #include <type_traits>
 
+#include "clear.hpp"
 #include "mat_common.hpp"
 #include "smallmat.hpp"
 
@@ -278,7 +279,7 @@ int mm_grass_pdist_bwd(int dtype, const void* x, const void* g, int64_t n, int N
   if (!g && mm_pair_offset(n, row_end) > mm_pair_offset(n, row_begin)) return MM_ERR_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
   constexpr int TI = 32;
-  hipError_t e = hipMemsetAsync(ws, 0, mm_grass_pdist_ws_bytes(dtype, n, N, p), st);
+  hipError_t e = clear_async(ws, mm_grass_pdist_ws_bytes(dtype, n, N, p), st);   // (a kernel: clear.hpp says why)
   if (e != hipSuccess) return int(e);
   MMM_DISPATCH_T(dtype, MMM_DISPATCH_NP_P(N, p, {
     if (row_end > row_begin) {

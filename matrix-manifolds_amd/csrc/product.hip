@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/mm_manifolds.h"
+#include "clear.hpp"
 #include "loss.hpp"
 #include "smallmat.hpp"
 
@@ -89,7 +90,7 @@ int product_loss_t(int loss_kind, int nf, const void* const* d2, const void* tar
     pa.g[k] = k < nf ? static_cast<T*>(g_out[k]) : nullptr;
   }
   T* slots = static_cast<T*>(ws);
-  hipError_t e = hipMemsetAsync(slots, 0, sizeof(T) * size_t(1 + nf) * kLossSlots, st);
+  hipError_t e = clear_async(slots, sizeof(T) * size_t(1 + nf) * kLossSlots, st);   // (a kernel: clear.hpp says why)
   if (e != hipSuccess) return int(e);
   LossArgs<T> la{nullptr, T(alpha), T(eps), terms, slots, loss_params};
   if (npairs > 0) {

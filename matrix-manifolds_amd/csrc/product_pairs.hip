@@ -27,6 +27,7 @@
 #include <cstdlib>
 
 #include "../../include/mm_manifolds.h"
+#include "clear.hpp"
 #include "loss.hpp"
 #include "product_args.hpp"
 #include "product_step.hpp"
@@ -738,7 +739,7 @@ int product_pairs_t(int loss_kind, int nf, const int* kinds, const int* dims, co
     }
   }
   if (!(flags & MM_WS_CLEAN)) {
-    hipError_t e = hipMemsetAsync(slots, 0, sizeof(T) * (size_t(1 + nf) * kLossSlots + acc_elems), st);
+    hipError_t e = clear_async(slots, sizeof(T) * (size_t(1 + nf) * kLossSlots + acc_elems), st);   // (a kernel: clear.hpp says why)
     if (e != hipSuccess) return int(e);
   }
   if (step)

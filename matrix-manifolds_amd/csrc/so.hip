@@ -30,6 +30,7 @@
 #include <climits>
 
 #include "../../include/mm_manifolds.h"
+#include "clear.hpp"
 #include "loss.hpp"
 #include "mat_common.hpp"
 #include "smallmat.hpp"
@@ -309,7 +310,7 @@ int launch_sym(const T* x, const T* target, int64_t n, int64_t rb, int64_t re, L
 }
 
 // The backward of the pair vector (loss = MM_LOSS_NONE: `target` is the upstream gradient, no loss record) and the fused objective
-// behind their four entry points, which check and act in the same order: memset, the pair kernel if the range has pairs, the
+// behind their four entry points, which check and act in the same order: the clear kernel, the pair kernel if the range has pairs, the
 // finalize launch over the table.  sub: a node minibatch (n = bs, idx needed where there are pairs); else n_total = n, idx null.
 static int pdist_sym(int dtype, int loss, const void* x, const void* target, const void* scale_raw, int64_t n, int64_t n_max, int N,
                      int64_t rb, int64_t re, int squared, double alpha, double eps, int terms, const double* loss_params,
@@ -321,7 +322,7 @@ static int pdist_sym(int dtype, int loss, const void* x, const void* target, con
   if (pairs && (!target || (sub && !idx))) return MM_ERR_ARG;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const size_t slot_bytes = loss == MM_LOSS_NONE ? 0 : 2 * kLossSlots * (dtype == MM_F64 ? 8 : 4);
-  hipError_t e = hipMemsetAsync(ws, 0, acc_bytes(dtype, n_total, N) + slot_bytes, st);
+  hipError_t e = clear_async(ws, acc_bytes(dtype, n_total, N) + slot_bytes, st);   // (a kernel: clear.hpp says why)
   if (e != hipSuccess) return int(e);
   MMM_DISPATCH_T(dtype, MMSO_DISPATCH_N(N, {
     T* acc = static_cast<T*>(ws);

@@ -18,6 +18,7 @@
 #include <type_traits>
 
 #include "../../include/mm_manifolds.h"
+#include "clear.hpp"
 #include "prof.hpp"
 #include "smallmat.hpp"
 #include "loss.hpp"
@@ -192,7 +193,9 @@ __global__ void vec_pdist_finalize_kernel(const T* __restrict__ x, const T* __re
     if (KIND == MM_EUCLIDEAN) r = T(2) * (acc[size_t(MP) * n + j] * x[size_t(j) * m + k] - s);  // sum w 2(x_j - x_i)
     else if (KIND == MM_LORENTZ) r = (k == 0) ? s : -s;                                           // dq/dx_j = -J x_i
     else r = s;
-    grad[size_t(j) * m + k] = r;
+    // (+ 0: a node no pair touched has s = +0 and would leave as -0 through the negations above; -0 + +0 = +0 under round to
+    // nearest, every other value is unchanged — rows outside a minibatch are +0 bit for bit, as in the other families)
+    grad[size_t(j) * m + k] = r + T(0);
   }
 }
 
@@ -597,7 +600,7 @@ int vec_bwd_t(const T* x, const T* g, int64_t n, int m, int64_t rb, int64_t re, 
         max_y = 65535;
       if (n > kSpdMaxNodes || (n + TI - 1) / TI > int64_t(max_y)) return MM_ERR_UNSUPPORTED;
     }
-    hipError_t e = hipMemsetAsync(acc, 0, sizeof(T) * (size_t(n) * (MP + 1) + 2 * kLossSlots), st);
+    hipError_t e = clear_async(acc, sizeof(T) * (size_t(n) * (MP + 1) + 2 * kLossSlots), st);   // (a kernel: clear.hpp says why)
     if (e != hipSuccess) return int(e);
     la.slots = slots;
     if (re > rb) {
@@ -637,7 +640,7 @@ int vec_loss_subset_t(int loss_kind, const T* x, const T* dense, const T* scale_
   T* acc = static_cast<T*>(ws);
   T* slots = acc + size_t(n_total) * (MP + 1);
   LossArgs<T> la{scale_raw, T(alpha), T(eps), terms, slots, loss_params};
-  hipError_t e = hipMemsetAsync(acc, 0, sizeof(T) * (size_t(n_total) * (MP + 1) + 2 * kLossSlots), st);
+  hipError_t e = clear_async(acc, sizeof(T) * (size_t(n_total) * (MP + 1) + 2 * kLossSlots), st);   // (a kernel: clear.hpp says why)
   if (e != hipSuccess) return int(e);
   if (re > rb && bs > 1) {
     const dim3 grid(int((bs + kVBlock - 1) / kVBlock), int((bs + rows - 1) / rows));

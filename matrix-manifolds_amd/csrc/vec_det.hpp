@@ -245,7 +245,10 @@ __global__ __launch_bounds__(kNodeBlock) void finalize_kernel(const T* __restric
 
 // ---- node minibatch: the table's gradient cleared to +0 before finalize stores the batch's rows -----------------------------------
 // (a kernel, not hipMemsetAsync: replayed from a captured graph, the memset node of this call left grad_x [200, 64] full of
-// foreign bytes on the SECOND replay on an MI355X — the loss record and the first replay were right; profiles/vec_deterministic.md)
+// foreign bytes on the SECOND replay on an MI355X — the loss record and the first replay were right.  The memset node IS the
+// cause: tests/test_replay_gpu.py reproduces it at nine other hipMemsetAsync sites of the library, at regions from 2.5 KB to
+// 52 KB, on every replay after the first and never eagerly, and each site is right once its memset is mm::clear_async (clear.hpp);
+// profiles/replay.md)
 template <typename T>
 __global__ __launch_bounds__(256) void clear_kernel(T* __restrict__ p, size_t count) {
   const size_t t = size_t(blockIdx.x) * 256 + threadIdx.x;

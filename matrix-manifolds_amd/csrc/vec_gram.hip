@@ -18,6 +18,7 @@
 #include <cstdlib>
 
 #include "../../include/mm_manifolds.h"
+#include "clear.hpp"
 #include "prof.hpp"
 #include "stamp.hpp"
 #include "smallmat.hpp"
@@ -822,7 +823,7 @@ __global__ void gram_loss_finalize_kernel(T* __restrict__ slots, const T* __rest
 // or fused objective (`g` = targets; la.slots must be zeroed [2][kLossSlots]).
 int vec_gram_bwd_launch(int kind, int loss_kind, const float* xp, const float* gp, int64_t n, int m, int64_t row_begin,
                         int64_t row_end, int squared, float* op, LossArgs<float> la, hipStream_t st) {
-  hipError_t e = hipMemsetAsync(op, 0, sizeof(float) * size_t(n) * m, st);
+  hipError_t e = clear_async(op, sizeof(float) * size_t(n) * m, st);   // (a kernel: clear.hpp says why)
   if (e != hipSuccess) return int(e);
   if (mm_pair_offset(n, row_end) == mm_pair_offset(n, row_begin)) return MM_OK;
   const int nT = int((n + 31) / 32);
