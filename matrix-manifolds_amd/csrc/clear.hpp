@@ -4,8 +4,11 @@
 // filled it with foreign, non-zero words on every later one (MI355X; tests/test_replay_gpu.py, profiles/replay.md: the
 // accumulators of csrc/so.hip, mat.hip, grass_loss.hip, grass_loss_subset.hip, vec.hip, vec_gram.hip, product.hip and
 // product_pairs.hip came back as 2.5e35 per element in one run and as small non-zero values in another, eager calls and the
-// first replay always right).  A kernel node carries its arguments
-// in the graph and has shown no such behaviour (vec_det::clear_kernel, stereo::subset_clear_kernel).
+// first replay always right).  A kernel node carries its arguments in the graph and has shown no such behaviour.
+//
+// THE LIBRARY'S RULE: no memset node, ever, whatever the size of the region — csrc/ calls hipMemsetAsync nowhere.  Every clear
+// goes through clear_async, down to the one- and two-word records of an empty table; stereo::subset_clear_kernel, which clears
+// several factors' gradients in one launch, is the one clear with a kernel of its own.
 #pragma once
 
 #include <hip/hip_runtime.h>

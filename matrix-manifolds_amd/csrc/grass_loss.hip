@@ -34,7 +34,7 @@ int launch_loss(const T* x, const T* target, int64_t n, int N, int64_t rb, int64
   if (gx <= 0 || gy <= 0) return MM_OK;
   grass_loss_sym_kernel<T, NP, P, LOSS, false><<<dim3(unsigned(gx * gy)), dim3(64), 0, st>>>(x, target, int(n), N, int(rb), int(re),
                                                                                            int(gx), jb0, la, acc, int(n), nullptr);
-  MMM_CHECK();
+  MM_CHECK_LAUNCH();
   return MM_OK;
 }
 
@@ -85,7 +85,7 @@ int mm_grass_pdist_loss(int dtype, int loss_kind, const void* x, const void* tar
     }
     grass_loss_finalize_kernel<T><<<dim3(unsigned((n + 127) / 128)), dim3(128), 0, st>>>(acc, int(n), N * p, static_cast<T*>(grad_x),
                                                                                         slots, sr, static_cast<T*>(loss_out));
-    MMM_CHECK(); return MM_OK; }))
+    MM_CHECK_LAUNCH(); return MM_OK; }))
 }
 
 }  // extern "C"

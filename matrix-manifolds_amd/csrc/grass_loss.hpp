@@ -58,7 +58,7 @@ __global__ __launch_bounds__(64) void grass_loss_sym_kernel(const T* __restrict_
 #pragma unroll
     for (int c = 0; c < P; ++c) a[r][c] = T(0);
   T loss_acc = T(0), ds_acc = T(0);
-  const int64_t base = SUB ? 0 : moff(n, row_begin);
+  const int64_t base = SUB ? 0 : pair_off(n, row_begin);
   const int ilast = min(i1, jbase + 63);   // rows from here on have no column in this block
   for (int i = i0; i < ilast; ++i) {
     T xi[NP][P], gm[P][P], dg[P][P];
@@ -69,7 +69,7 @@ __global__ __launch_bounds__(64) void grass_loss_sym_kernel(const T* __restrict_
     T tg = T(1);
     if (valid) {
       if constexpr (SUB) tg = target[size_t(ni) * size_t(n_total) + size_t(loss_node_of(idx, j, n_total))];
-      else tg = target[moff(n, i) - base + (j - i - 1)];
+      else tg = target[pair_off(n, i) - base + (j - i - 1)];
     }
     gram<T, NP, P>(xi, xj, gm);  // x_i^T x_j ; d/dx_j = x_i dG, d/dx_i = x_j dG^T
     const T v = grass_pair<T, P, true>(gm, dg);

@@ -31,7 +31,7 @@ int launch_subset(const T* x, const T* dense, int64_t n_total, const int64_t* id
     if (gx <= 0 || gy <= 0) return MM_OK;
     grass_loss_sym_kernel<T, NP, P, LOSS, true><<<dim3(unsigned(gx * gy)), dim3(64), 0, st>>>(x, dense, int(bs), N, int(rb), int(re),
                                                                                          int(gx), jb0, la, acc, int(n_total), idx);
-    MMM_CHECK();
+    MM_CHECK_LAUNCH();
     return MM_OK;
   } else {
     return MM_ERR_UNSUPPORTED;
@@ -84,7 +84,7 @@ int mm_grass_pdist_loss_subset(int dtype, int loss_kind, const void* x, const vo
     grass_loss_finalize_kernel<T><<<dim3(unsigned((n_total + 127) / 128)), dim3(128), 0, st>>>(acc, int(n_total), N * p,
                                                                                               static_cast<T*>(grad_x), slots, sr,
                                                                                               static_cast<T*>(loss_out));
-    MMM_CHECK(); return MM_OK; }))
+    MM_CHECK_LAUNCH(); return MM_OK; }))
 }
 
 }  // extern "C"

@@ -61,7 +61,8 @@ __device__ __forceinline__ T loss_term(T m, T target, const LossArgs<T>& la, T& 
 }
 
 // Sums the kLossSlots partial sums (fp64), writes loss_out = {loss, d loss / d scale_raw} and leaves the
-// slots clean.  Called by the first wavefront of block 0 of a finalize kernel.
+// slots clean.  Called by the first wavefront of block 0 of a finalize kernel.  (The bit-deterministic modes have one slot per
+// workgroup, written by every launch: the head of spd_det:: / vec_det::finalize_kernel, det_common.hpp.)
 template <typename T>
 __device__ __forceinline__ void loss_finalize(T* __restrict__ slots, const T* __restrict__ scale_raw,
                                               T* __restrict__ loss_out) {

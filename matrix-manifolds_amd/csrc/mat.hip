@@ -140,13 +140,13 @@ __global__ __launch_bounds__(kBlk) void grass_pdist_fwd_kernel(const T* __restri
   const bool jin = j < n;
   T xj[NP][P];
   load<T, NP, P>(x + size_t(jin ? j : 0) * N * P, N, xj);
-  const int64_t base = moff(n, row_begin);
+  const int64_t base = pair_off(n, row_begin);
   for (int i = i0; i < i1; ++i) {
     T xi[NP][P], gm[P][P], dg[P][P];
     load<T, NP, P>(x + size_t(i) * N * P, N, xi);  // wave-uniform -> scalar loads
     gram<T, NP, P>(xi, xj, gm);
     const T v = grass_pair<T, P, false>(gm, dg);
-    if (jin && j > i) out[moff(n, i) - base + (j - i - 1)] = squared ? v : Num<T>::sqrt(v);
+    if (jin && j > i) out[pair_off(n, i) - base + (j - i - 1)] = squared ? v : Num<T>::sqrt(v);
   }
 }
 
@@ -166,7 +166,7 @@ __global__ __launch_bounds__(kBlk) void grass_pdist_bwd_kernel(const T* __restri
   for (int r = 0; r < NP; ++r)
 #pragma unroll
     for (int c = 0; c < P; ++c) a[r][c] = T(0);
-  const int64_t base = moff(n, row_begin);
+  const int64_t base = pair_off(n, row_begin);
   for (int i = i0; i < i1; ++i) {
     T xi[NP][P], gm[P][P], dg[P][P];
     load<T, NP, P>(x + size_t(i) * N * P, N, xi);
@@ -174,7 +174,7 @@ __global__ __launch_bounds__(kBlk) void grass_pdist_bwd_kernel(const T* __restri
     const bool valid = jin && i != j && (up ? (i >= row_begin && i < row_end) : jown);
     const int lo = up ? i : j, hi = up ? j : i;
     T w = T(0);
-    if (valid) w = g[moff(n, lo) - base + (hi - lo - 1)];
+    if (valid) w = g[pair_off(n, lo) - base + (hi - lo - 1)];
     gram<T, NP, P>(xi, xj, gm);  // x_i^T x_j ; d/dx_j = x_i dG
     const T v = grass_pair<T, P, true>(gm, dg);
     if (!squared) w *= T(0.5) * Nm::rsqrt(v);
@@ -233,7 +233,7 @@ int mm_mat_map(int dtype, int kind, int op, const void* x, const void* u, int64_
   MMM_DISPATCH_T(dtype, MMM_DISPATCH_NP_P(N, p, {
     mat_map_kernel<T, NP, P><<<dim3(nb), dim3(64), 0, st>>>(kind, op, static_cast<const T*>(x),
         static_cast<const T*>(u), cnt, N, static_cast<T*>(out));
-    MMM_CHECK(); return MM_OK; }))
+    MM_CHECK_LAUNCH(); return MM_OK; }))
 }
 
 int mm_grass_dist(int dtype, const void* x, const void* y, const void* g, int64_t cnt, int N, int p, int squared,
@@ -249,7 +249,7 @@ int mm_grass_dist(int dtype, const void* x, const void* y, const void* g, int64_
     grass_dist_kernel<T, NP, P><<<dim3(nb), dim3(64), 0, st>>>(static_cast<const T*>(x), static_cast<const T*>(y),
         static_cast<const T*>(g), cnt, N, squared, static_cast<T*>(out), static_cast<T*>(grad_x),
         static_cast<T*>(grad_y));
-    MMM_CHECK(); return MM_OK; }))
+    MM_CHECK_LAUNCH(); return MM_OK; }))
 }
 
 int mm_grass_pdist_fwd(int dtype, const void* x, int64_t n, int N, int p, int64_t row_begin, int64_t row_end,
@@ -267,7 +267,7 @@ int mm_grass_pdist_fwd(int dtype, const void* x, int64_t n, int N, int p, int64_
   MMM_DISPATCH_T(dtype, MMM_DISPATCH_NP_P(N, p, {
     grass_pdist_fwd_kernel<T, NP, P, TI><<<dim3(gx, gy), dim3(kBlk), 0, st>>>(static_cast<const T*>(x), int(n), N,
         int(row_begin), int(row_end), squared, static_cast<T*>(out));
-    MMM_CHECK(); return MM_OK; }))
+    MM_CHECK_LAUNCH(); return MM_OK; }))
 }
 
 int mm_grass_pdist_bwd(int dtype, const void* x, const void* g, int64_t n, int N, int p, int64_t row_begin,
@@ -286,11 +286,11 @@ int mm_grass_pdist_bwd(int dtype, const void* x, const void* g, int64_t n, int N
       grass_pdist_bwd_kernel<T, NP, P, TI><<<dim3(int((n + kBlk - 1) / kBlk), int((n + TI - 1) / TI)), dim3(kBlk), 0, st>>>(
           static_cast<const T*>(x), static_cast<const T*>(g), int(n), N, int(row_begin), int(row_end), squared,
           static_cast<T*>(ws));
-      MMM_CHECK();
+      MM_CHECK_LAUNCH();
     }
     grass_finalize_kernel<T><<<dim3(int((n + 127) / 128)), dim3(128), 0, st>>>(static_cast<const T*>(ws), int(n),
                                                                               N * p, static_cast<T*>(grad_x));
-    MMM_CHECK(); return MM_OK; }))
+    MM_CHECK_LAUNCH(); return MM_OK; }))
 }
 
 }  // extern "C"

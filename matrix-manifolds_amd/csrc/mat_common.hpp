@@ -8,6 +8,7 @@
 #include <type_traits>
 
 #include "../../include/mm_manifolds.h"
+#include "launch.hpp"
 #include "smallmat.hpp"
 
 namespace mm {
@@ -429,15 +430,8 @@ __device__ __forceinline__ void exp_op(const T (&xa)[NP][P], const T (&ua)[NP][P
 }
 
 constexpr int kBlk = 128;
-__host__ __device__ inline int64_t moff(int64_t n, int64_t row) { return row * (2 * n - row - 1) / 2; }
 
 constexpr int pad_rows(int N) { return N <= 4 ? 4 : N <= 6 ? 6 : 9; }
-
-#define MMM_CHECK()                                    \
-  do {                                                 \
-    hipError_t e_ = hipGetLastError();                 \
-    if (e_ != hipSuccess) return static_cast<int>(e_); \
-  } while (0)
 
 #define MMM_DISPATCH_NP_P(N, p, ...)                                            \
   switch (pad_rows(N) * 10 + (p)) {                                             \

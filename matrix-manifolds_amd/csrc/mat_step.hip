@@ -81,7 +81,7 @@ int rsgd_launch(int dtype, int kind, int retr, const void* x, const void* egrad,
     mat_rsgd_kernel<T, NP, P, MOMENTUM><<<dim3(nb), dim3(64), 0, st>>>(kind, op, static_cast<const T*>(x),
         static_cast<const T*>(egrad), static_cast<T*>(buf), cnt, N, T(lr), T(momentum), T(dampening), T(max_grad_norm),
         static_cast<T*>(x_new));
-    MMM_CHECK(); return MM_OK; }))
+    MM_CHECK_LAUNCH(); return MM_OK; }))
 }
 
 // The step's coefficients are formed by one thread per workgroup and handed over through LDS: the two fp64 pow() stay out of
@@ -179,7 +179,7 @@ int mm_mat_radam_step(int dtype, int kind, int retr_op, const void* x, const voi
     const mm::AdamArgs<T> a{T(lr), T(beta1), T(beta2), T(eps), T(max_grad_norm), nc, exact, step, ticket};
     mat_radam_kernel<T, NP, P><<<dim3(nb), dim3(64), 0, st>>>(kind, op, static_cast<const T*>(x), static_cast<const T*>(egrad),
         static_cast<T*>(exp_avg), static_cast<T*>(exp_avg_sq), cnt, N, a, beta1, beta2, static_cast<T*>(x_new));
-    MMM_CHECK(); return MM_OK; }))
+    MM_CHECK_LAUNCH(); return MM_OK; }))
 }
 
 }  // extern "C"

@@ -30,6 +30,8 @@
 #include <cmath>
 
 #include "../../include/mm_manifolds.h"
+#include "clear.hpp"
+#include "launch.hpp"
 #include "smallmat.hpp"
 
 namespace mm {
@@ -42,7 +44,6 @@ constexpr int kF = 6;                   // values per record / table row
 constexpr int kMergeBlk = 256;
 constexpr int64_t kMaxNodes = 32768;    // pair offsets stay below 2^31 elements; the fp64 slab is 0.8 GB there
 
-__host__ __device__ inline int64_t poff(int64_t n, int64_t row) { return row * (2 * n - row - 1) / 2; }
 inline size_t round256(size_t b) { return (b + 255) & ~size_t(255); }
 inline size_t slab_bytes(size_t el, int64_t n) { return round256(el * kF * size_t((n + kB - 1) / kB + 1) * size_t(n)); }
 inline size_t table_bytes(size_t el, int64_t n) { return round256(el * kF * size_t(n)); }
@@ -132,14 +133,14 @@ __global__ __launch_bounds__(kB * kWaves) void sne_stats_kernel(const T* __restr
   // ic = min(i, n - 2), jc = min(max(j, ic + 1), n - 1); that IS its pair when it has one — at a 32-bit offset from the first
   // row's slice; a pair outside the triangle then becomes theta = -inf, delta = 0.
   const int ic0 = min(i0, n - 2);
-  const int64_t base0 = poff(n, ic0) - ic0 - 1;
+  const int64_t base0 = pair_off(n, ic0) - ic0 - 1;
   const T* __restrict__ g0 = g + base0;
   const T* __restrict__ m0 = m + base0;
   T tx[kRows], tz[kRows];
 #pragma unroll
   for (int r = 0; r < kRows; ++r) {
     const int ic = min(i0 + r, n - 2);
-    const int off = int(poff(n, ic) - ic - 1 - base0) + min(max(j, ic + 1), n - 1);
+    const int off = int(pair_off(n, ic) - ic - 1 - base0) + min(max(j, ic + 1), n - 1);
     thetas<T, MODE>(g0[off], m0[off], alpha, tx[r], tz[r]);
   }
   T dl[kRows];
@@ -306,7 +307,7 @@ __global__ __launch_bounds__(kB * kWaves) void sne_grad_kernel(const T* __restri
   const int i1 = min(i0 + kRows, n);
   for (int i = i0; i < i1; ++i) {
     if (j <= i) continue;
-    const int64_t idx = poff(n, i) + (j - i - 1);
+    const int64_t idx = pair_off(n, i) + (j - i - 1);
     T tx, tz;
     thetas<T, MODE>(g[idx], m[idx], alpha, tx, tz);
     const T pxr = Num<T>::exp((tx - table[i]) - table[ns + i]), pxc = Num<T>::exp((tx - cMx) - cLx);
@@ -359,7 +360,7 @@ int mm_sne_kl_loss(int dtype, int mode, const void* target, const void* m, int64
   if (n > kMaxNodes) return MM_ERR_UNSUPPORTED;
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (n < 2) {   // no pair: the loss is 0 and the gradient has no entry
-    const hipError_t e = hipMemsetAsync(loss_out, 0, dtype == MM_F64 ? 8 : 4, st);
+    const hipError_t e = mm::clear_async(loss_out, dtype == MM_F64 ? 8 : 4, st);
     return e == hipSuccess ? MM_OK : int(e);
   }
   if (dtype == MM_F32) {

@@ -40,7 +40,6 @@ namespace mm {
 namespace so {
 
 using mat::kBlk;
-using mat::moff;
 
 constexpr int kTI = 16;   // rows per tile
 constexpr int kMaxDim = 4;
@@ -119,7 +118,7 @@ __global__ __launch_bounds__(kBlk) void so_pdist_fwd_kernel(const T* __restrict_
   T xj[N][N];
   if constexpr (SUB) load<T, N>(x + size_t(node_of(idx, jin ? j : 0, n_total)) * N * N, xj);
   else load<T, N>(x + size_t(jin ? j : 0) * N * N, xj);
-  const int64_t base = moff(n, row_begin);
+  const int64_t base = pair_off(n, row_begin);
   for (int i = i0; i < i1; ++i) {
     T xi[N][N], D[N][N], dD[N][N];
     int ni = i;
@@ -127,7 +126,7 @@ __global__ __launch_bounds__(kBlk) void so_pdist_fwd_kernel(const T* __restrict_
     load<T, N>(x + size_t(ni) * N * N, xi);  // wave-uniform -> scalar loads
     diff<T, N>(xj, xi, D);
     const T v = so_pair<T, N, false>(D, dD);
-    if (jin && j > i) out[moff(n, i) - base + (j - i - 1)] = squared ? v : Num<T>::sqrt(v);
+    if (jin && j > i) out[pair_off(n, i) - base + (j - i - 1)] = squared ? v : Num<T>::sqrt(v);
   }
 }
 
@@ -162,7 +161,7 @@ __global__ __launch_bounds__(64) void so_pdist_sym_kernel(const T* __restrict__ 
 #pragma unroll
     for (int c = 0; c < N; ++c) a[r][c] = T(0);
   T loss_acc = T(0), ds_acc = T(0);
-  const int64_t base = moff(n, row_begin);
+  const int64_t base = pair_off(n, row_begin);
   const int ilast = min(i1, jbase + 63);   // rows from here on have no column in this block
   for (int i = i0; i < ilast; ++i) {
     T xi[N][N], D[N][N], dD[N][N];
@@ -173,7 +172,7 @@ __global__ __launch_bounds__(64) void so_pdist_sym_kernel(const T* __restrict__ 
     T tg = LOSS == MM_LOSS_NONE ? T(0) : T(1);
     if (valid) {
       if constexpr (SUB && LOSS != MM_LOSS_NONE) tg = target[size_t(ni) * size_t(n_total) + size_t(node_of(idx, j, n_total))];
-      else tg = target[moff(n, i) - base + (j - i - 1)];
+      else tg = target[pair_off(n, i) - base + (j - i - 1)];
     }
     diff<T, N>(xj, xi, D);
     const T v = so_pair<T, N, true>(D, dD);
@@ -290,7 +289,7 @@ static int launch_fwd(int dtype, const void* x, int64_t n, int N, int64_t rb, in
                                                                          static_cast<T*>(out), int(n_total), idx);
     else so_pdist_fwd_kernel<T, N, false><<<grid, dim3(kBlk), 0, st>>>(static_cast<const T*>(x), int(n), int(rb), int(re), squared,
                                                                       static_cast<T*>(out), int(n_total), idx);
-    MMM_CHECK(); return MM_OK; }))
+    MM_CHECK_LAUNCH(); return MM_OK; }))
 }
 
 // null idx: the full batch (n_total = n)
@@ -305,7 +304,7 @@ int launch_sym(const T* x, const T* target, int64_t n, int64_t rb, int64_t re, L
                                                                                     la, acc, int(n_total), idx);
   else so_pdist_sym_kernel<T, N, LOSS, SQUARED, false><<<grid, dim3(64), 0, st>>>(x, target, int(n), int(rb), int(re), int(gx), jb0,
                                                                                  la, acc, int(n_total), idx);
-  MMM_CHECK();
+  MM_CHECK_LAUNCH();
   return MM_OK;
 }
 
@@ -340,7 +339,7 @@ static int pdist_sym(int dtype, int loss, const void* x, const void* target, con
     }
     so_finalize_kernel<T><<<dim3(unsigned((n_total + 127) / 128)), dim3(128), 0, st>>>(acc, int(n_total), N * N, static_cast<T*>(grad_x),
                                                                                       slots, sr, static_cast<T*>(loss_out));
-    MMM_CHECK(); return MM_OK; }))
+    MM_CHECK_LAUNCH(); return MM_OK; }))
 }
 
 }  // namespace so
@@ -364,7 +363,7 @@ int mm_so_map(int dtype, int op, const void* x, const void* u, int64_t cnt, int 
   MMM_DISPATCH_T(dtype, MMSO_DISPATCH_N(N, {
     so_map_kernel<T, N><<<dim3(nb), dim3(64), 0, st>>>(op, static_cast<const T*>(x), static_cast<const T*>(u), cnt,
                                                      static_cast<T*>(out));
-    MMM_CHECK(); return MM_OK; }))
+    MM_CHECK_LAUNCH(); return MM_OK; }))
 }
 
 int mm_so_dist(int dtype, const void* x, const void* y, const void* g, int64_t cnt, int N, int squared, void* out, void* grad_x,
@@ -381,7 +380,7 @@ int mm_so_dist(int dtype, const void* x, const void* y, const void* g, int64_t c
     so_dist_kernel<T, N><<<dim3(nb), dim3(64), 0, st>>>(static_cast<const T*>(x), static_cast<const T*>(y), static_cast<const T*>(g),
                                                       cnt, squared, static_cast<T*>(out), static_cast<T*>(grad_x),
                                                       static_cast<T*>(grad_y));
-    MMM_CHECK(); return MM_OK; }))
+    MM_CHECK_LAUNCH(); return MM_OK; }))
 }
 
 size_t mm_so_pdist_ws_bytes(int dtype, int64_t n, int N) {

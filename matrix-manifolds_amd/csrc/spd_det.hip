@@ -1,6 +1,7 @@
 // The bit-deterministic SPD(d) pair gradients (spd_det.hpp): C entry points and their instantiations, every d = 2 ... 9 in fp32
 // and fp64 x {upstream gradient of d^2, of d, stress, quotient}.  A translation unit of its own: compiled in parallel with the
 // atomic kernels, whose instantiations it does not touch.
+#include "clear.hpp"
 #include "spd_det.hpp"
 
 using namespace mm;
@@ -52,7 +53,7 @@ int mm_spd_pdist_loss_det(int dtype, int loss_kind, const void* x, const void* t
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (n == 0) {
     const size_t es = dtype == MM_F64 ? 8 : 4;
-    hipError_t e = hipMemsetAsync(loss_out, 0, 2 * es, st);
+    hipError_t e = clear_async(loss_out, 2 * es, st);
     return e == hipSuccess ? MM_OK : int(e);
   }
   MM_DISPATCH(dtype, d,

@@ -1,56 +1,27 @@
-// SPD(d) pair gradients WITHOUT float atomics: the bit-deterministic mode next to spd_pdist_bwd_kernel (spd_pair.hpp; SURVEY.md
-// section 7, "Scatter of pair gradients", option b).
+// SPD(d) pair gradients WITHOUT float atomics: the bit-deterministic mode next to spd_pdist_bwd_kernel (spd_pair.hpp).  The form,
+// the loss record and the determinism contract are det_common.hpp's; this file holds what is SPD's own.
 //
-// Form: BOTH ORDERS, COLUMN-OWNED.  A lane owns one column node c and walks a chunk of rows r, r < c and r > c alike; per visited
-// pair it does the column side of the atomic backward:
+// Per visited pair a lane does the column side of the atomic backward:
 //     A = L_r^-1 X_c L_r^-T,   M = 2 g log A,   S_c += L_r^-T M L_r^T
-// d^2(X_r, X_c) is symmetric in its arguments, so the column-side formula applied to EVERY r != c is the whole gradient:
-// grad_c = sym(S_c X_c^-1).  There is no row-side sum — no reduction across lanes, no accM, no atomics — and the price is the
-// logarithm of every pair twice.  A lane's d^2 sums of a chunk leave with plain stores into slab[chunk][entry][c] (coalesced per
-// entry); the finalize kernel (one thread per node) adds a node's chunk records in chunk order, applies X_c^-1 and the
-// symmetrisation and writes grad_x.  The loss term and sum dloss/dm d^2 are counted in the r < c visit only, reduced per
-// workgroup in a fixed order (butterfly inside a wavefront, wavefronts in index order) and stored to ONE slot per workgroup;
-// finalize adds the slots in fp64, lane t the slots t, t + 64, ... in index order, the 64 lane sums through the same butterfly.
-//
-// Every order of summation is a pure function of (dtype, n, d) (DetGeometry below): never of the row range, the device, an
-// occupancy query or the environment.  The four wavefronts of a workgroup own DIFFERENT columns (64 each) and walk the same rows:
-// no partial sums of one column are shared between wavefronts, so nothing is folded through LDS but the loss record.
+// d^2(X_r, X_c) is symmetric in its arguments, so summed over EVERY r != c this is the whole gradient: grad_c = sym(S_c X_c^-1),
+// applied by the finalize kernel to the d^2 sums of a node's chunk records.  The row operand {L_r^-1, L_r} is read with scalar
+// loads.  Every order of summation is a pure function of (dtype, n, d): geometry() below.
 //
 // The logarithm of a pair takes the gates and device functions of the atomic kernel (log_pair2_chol; close_gate / log_close, the
 // recentred series, log_cayley, pair_core with the fp32 second solve; log_close_mat / log_centred_mat), one column per lane at
 // every D, so the two modes agree to rounding.  The dispatch is written out here: spd_pdist_bwd_kernel is not touched.
 #pragma once
+#include "det_common.hpp"
 #include "spd_pair.hpp"
 
 namespace mm {
 namespace spd_det {
 
-// ---- launch geometry: a pure function of (element size, n, d) ------------------------------------------------------------
-constexpr int kWaves = 4;                        // wavefronts of a workgroup; each owns 64 columns of its own
-constexpr int kCols = 64 * kWaves;               // columns per workgroup
-constexpr int kMinRows = 8;                      // rows per chunk at least: a chunk pays a column prologue and d^2 stores per lane
-constexpr int64_t kTargetWgs = 1024;             // the grid is sized towards this many workgroups (four per CU of an MI355X)
-constexpr size_t kSlabCap = size_t(64) << 20;    // B of mm_spd_pdist_det_ws_bytes: the slab is at most max(d^2 n sizeof(T), B)
-
-struct DetGeometry {
-  int64_t groups, chunks, rows;   // column groups, row chunks, rows per chunk: (chunks - 1) rows < n <= chunks rows
-  size_t slab_bytes, slot_bytes;
-  size_t bytes() const { return slab_bytes + slot_bytes; }
-};
-inline DetGeometry geometry(size_t esz, int64_t n, int d) {
-  DetGeometry g{};
-  if (n < 1) { g.groups = 0; g.chunks = 1; g.rows = 1; g.slab_bytes = 0; g.slot_bytes = 0; return g; }
-  g.groups = (n + kCols - 1) / kCols;
-  int64_t want = (kTargetWgs + g.groups - 1) / g.groups;                     // falls as n grows
-  const size_t record = size_t(d) * d * size_t(n) * esz;                     // one chunk's records of all nodes
-  const int64_t cap = std::max<int64_t>(1, int64_t(kSlabCap / record));      // the slab stays within max(record, kSlabCap)
-  want = std::max<int64_t>(1, std::min(want, cap));
-  g.rows = std::max<int64_t>(kMinRows, (n + want - 1) / want);
-  g.chunks = (n + g.rows - 1) / g.rows;
-  g.slab_bytes = (size_t(g.chunks) * record + 63) / 64 * 64;
-  g.slot_bytes = (2 * size_t(g.groups) * size_t(g.chunks) * esz + 63) / 64 * 64;
-  return g;
-}
+using det::DetGeometry;
+using det::kCols;
+using det::kWaves;
+// one node's chunk record: d^2 sums; rows per chunk in steps of one
+inline DetGeometry geometry(size_t esz, int64_t n, int d) { return det::geometry(esz, size_t(d) * d * esz, n, 1); }
 
 // ---- one pair: M = 2 g log A (packed), g from the upstream gradient / the fused loss ---------------------------------------
 // `loaded`: upstream gradient or target of the pair (0 for a dead pair), `live`: the pair counts, `upper`: r < c (the visit
@@ -148,9 +119,7 @@ __device__ __forceinline__ void pair_m(const T (&li)[Packed<D>::NP], const T (&x
 // ---- the pair kernel ---------------------------------------------------------------------------------------------------
 // grid (groups, chunks); workgroup (x, y): columns [kCols x, kCols x + kCols), rows [rows y, rows y + rows) of ALL n rows.
 // A pair (r, c) is live iff r != c, c < n and row_begin <= min(r, c) < row_end; its upstream gradient / target sits at
-// pair_off(min) - base + (max - min - 1) of `g` (64-bit).  Rows that hold no live pair for the wavefront's columns are cut off
-// the walk — wave-uniformly, and without moving a sum: the order in which a lane adds its live pairs is the row order either way.
-// slab [chunks][D*D][n]; slots [2][groups * chunks].  Every record and every slot is written by every launch.
+// pair_off(min) - base + (max - min - 1) of `g` (64-bit).  The row cut is wave-uniform.  slab [chunks][D*D][n]; slots [2][groups * chunks].
 template <typename T, int D, int LOSS, bool SQ>
 __global__ __launch_bounds__(64 * kWaves) void pair_kernel(const T* __restrict__ nodeLC /* {L_r^-1, L_r} */,
                                                             const T* __restrict__ nodeY /* chol(X_c) */, const T* __restrict__ g,

@@ -1,6 +1,7 @@
 // Fused objective of a single SPD(d) factor (loss + both gradients in one pass over the pairs: objectives.py:16-45 on
 // spd.py:175-181) and its fused training step (spd_step.hpp): the LOSS instantiations of the backward pair kernel and the
 // per-point finalize / optimizer / tables kernel (spd_pair.hpp).  A translation unit of its own: compiled in parallel with spd.hip.
+#include "clear.hpp"
 #include "spd_pair.hpp"
 
 namespace mm {
@@ -56,7 +57,7 @@ int mm_spd_pdist_loss(int dtype, int loss_kind, const void* x, const void* targe
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (n == 0) {
     const size_t es = dtype == MM_F64 ? 8 : 4;
-    hipError_t e = hipMemsetAsync(loss_out, 0, 2 * es, st);
+    hipError_t e = clear_async(loss_out, 2 * es, st);
     return e == hipSuccess ? MM_OK : int(e);
   }
   MM_DISPATCH(dtype, d,

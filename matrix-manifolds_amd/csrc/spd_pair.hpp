@@ -1292,11 +1292,6 @@ __global__ void spd_fused_step_kernel(T* x, int n, StepRule<T> rule, StepFuse<T>
 }
 
 // ------------------------------------------------------------------ launchers
-#define MM_CHECK_LAUNCH()                         \
-  do {                                            \
-    hipError_t e_ = hipGetLastError();            \
-    if (e_ != hipSuccess) return static_cast<int>(e_); \
-  } while (0)
 
 // Threads per workgroup of the per-node kernels (prep, finalize): n = 5000 nodes are 40 workgroups of 128 or 79 of 64
 constexpr int kNodeBlock = 128;

@@ -3,6 +3,7 @@
 // (experiments/utils.py:3-40), trained the way the other factors are.  Kernels: spd_stein_loss.hpp; the divergence itself and
 // the plain forward / backward: spd_stein.hpp (instantiated by spd.hip).  A translation unit of its own: these
 // instantiations compile next to spd.hip / spd_loss.hip / spd_subset.hip.
+#include "clear.hpp"
 #include "spd_pair.hpp"
 
 namespace mm {
@@ -29,7 +30,7 @@ int mm_spd_stein_pdiv_loss(int dtype, int loss_kind, const void* x, const void* 
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (n == 0) {
     const size_t es = dtype == MM_F64 ? 8 : 4;
-    hipError_t e = hipMemsetAsync(loss_out, 0, 2 * es, st);
+    hipError_t e = clear_async(loss_out, 2 * es, st);
     return e == hipSuccess ? MM_OK : int(e);
   }
   MM_DISPATCH(dtype, d,
@@ -53,7 +54,7 @@ int mm_spd_stein_pdiv_loss_subset(int dtype, int loss_kind, const void* x, const
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (n_total == 0) {
     const size_t es = dtype == MM_F64 ? 8 : 4;
-    hipError_t e = hipMemsetAsync(loss_out, 0, 2 * es, st);
+    hipError_t e = clear_async(loss_out, 2 * es, st);
     return e == hipSuccess ? MM_OK : int(e);
   }
   MM_DISPATCH(dtype, d,

@@ -6,6 +6,7 @@
 // vector goes into the pair kernel (spd_pair.hpp, spd_pdist_bwd_kernel<..., SUB = true>): table rows, targets and
 // accumulator slots are addressed through it, and the per-node kernels over the FULL embedding produce the dense gradient.
 // A translation unit of its own: the SUB instantiations compile next to spd.hip / spd_loss.hip.
+#include "clear.hpp"
 #include "spd_pair.hpp"
 
 namespace mm {
@@ -45,7 +46,7 @@ int mm_spd_pdist_loss_subset(int dtype, int loss_kind, const void* x, const void
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (n_total == 0) {
     const size_t es = dtype == MM_F64 ? 8 : 4;
-    hipError_t e = hipMemsetAsync(loss_out, 0, 2 * es, st);
+    hipError_t e = clear_async(loss_out, 2 * es, st);
     return e == hipSuccess ? MM_OK : int(e);
   }
   MM_DISPATCH(dtype, d,

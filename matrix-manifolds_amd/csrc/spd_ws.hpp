@@ -8,6 +8,7 @@
 #include <cstdlib>
 
 #include "../../include/mm_manifolds.h"
+#include "launch.hpp"
 #include "loss.hpp"
 #include "smallmat.hpp"
 
@@ -68,8 +69,6 @@ template <typename T, int D> constexpr int bwd_waves() {
 #define MM_SPD_MAX_D 9   // (development builds: -DMM_SPD_MAX_D=5 compiles spd.hip three times faster)
 #endif
 constexpr int kSpdMaxD = MM_SPD_MAX_D;   // the reference's tests go to 9 (tests/test_spd.py:15,26,62,70); D >= 6 spills to scratch
-
-__host__ __device__ inline int64_t pair_off(int64_t n, int64_t row) { return row * (2 * n - row - 1) / 2; }
 
 // Workspace layout (T = element type, NP = d(d+1)/2):
 //   [0,64)            word 0 = number of non-PD points (written by mm_spd_status' reduction)
@@ -181,7 +180,6 @@ template <int TI, int BW = kBlock> inline dim3 fold_grid(int64_t n, int64_t rb, 
   }
   return dim3(gx > 0 ? gx : 1, (gy + 1) / 2 > 0 ? (gy + 1) / 2 : 1);
 }
-
 
 // ---- balanced walk of the upper triangle (backward kernels) ---------------------------------------------------------
 // Work is measured in ROWS OF COLUMN BLOCKS of bw = 64 or 128 columns: block c (columns bw c .. bw c + bw - 1) owns the

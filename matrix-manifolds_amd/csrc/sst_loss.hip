@@ -33,6 +33,7 @@
 #include <cmath>
 
 #include "../../include/mm_manifolds.h"
+#include "clear.hpp"
 #include "smallmat.hpp"
 
 namespace mm {
@@ -460,7 +461,7 @@ int mm_sst_kl_loss(int dtype, int mode, const void* target, const void* m, int64
   if (n > kMaxNodes) return MM_ERR_UNSUPPORTED;
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (n < 2) {   // no pair: the loss is 0 and the gradient has no entry
-    const hipError_t e = hipMemsetAsync(loss_out, 0, dtype == MM_F64 ? 8 : 4, st);
+    const hipError_t e = mm::clear_async(loss_out, dtype == MM_F64 ? 8 : 4, st);
     return e == hipSuccess ? MM_OK : int(e);
   }
   return dtype == MM_F32 ? dispatch<float>(mode, target, m, n, alpha, grad_out, loss_out, ws, st)

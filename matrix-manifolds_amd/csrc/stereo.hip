@@ -31,6 +31,8 @@
 
 #include "../../include/mm_manifolds.h"
 #include "adam.hpp"
+#include "clear.hpp"
+#include "launch.hpp"
 #include "loss.hpp"
 
 namespace mm {
@@ -46,7 +48,6 @@ constexpr double kEps = 1e-8;            // EPS (utils.py:13), both precisions
 
 template <typename T> struct Tile { static constexpr int rows = sizeof(T) == 4 ? 64 : 32; };
 
-__host__ __device__ inline int64_t poff(int64_t n, int64_t row) { return row * (2 * n - row - 1) / 2; }
 inline size_t round256(size_t b) { return (b + 255) & ~size_t(255); }
 
 template <typename T> struct M;
@@ -177,7 +178,7 @@ __global__ __launch_bounds__(kC* kWaves) void pdist_fwd_kernel(const T* __restri
   }
   const T sj = 1 - c * b;
   __syncthreads();
-  const int64_t base = poff(n, rb);
+  const int64_t base = pair_off(n, rb);
   // interior tiles (wholly above the diagonal and inside the table) store without a lane mask; diagonal and edge tiles mask
   auto rows = [&](auto masked) {
 #pragma unroll 4
@@ -191,7 +192,7 @@ __global__ __launch_bounds__(kC* kWaves) void pdist_fwd_kernel(const T* __restri
         q += d * d;
       }
       const T v = pair_value<T>(q, ss[il] * sj + c * q, c, squared != 0);
-      if (!decltype(masked)::value || (j > i && j < n)) out[poff(n, i) - base + (j - i - 1)] = v;
+      if (!decltype(masked)::value || (j > i && j < n)) out[pair_off(n, i) - base + (j - i - 1)] = v;
     }
   };
   if (bj > bi && bj * kC + kC <= n)
@@ -251,7 +252,7 @@ __global__ __launch_bounds__(kC* kWaves) void pdist_bwd_kernel(const T* __restri
   T cacc = 0;
   {
     const T b = sbc[lane], sj = 1 - c * b;
-    const int64_t base = poff(n, rb);
+    const int64_t base = pair_off(n, rb);
 #pragma unroll UNR
     for (int r = 0; r < RW; ++r) {
       const int il = wave * RW + r, i = bi * TR + il;
@@ -266,7 +267,7 @@ __global__ __launch_bounds__(kC* kWaves) void pdist_bwd_kernel(const T* __restri
       const bool live = j > i && j < n && i >= rb && i < re;
       T A = 0, At = 0, dcp = 0;
       if (live) {
-        const T gv = g[poff(n, i) - base + (j - i - 1)];
+        const T gv = g[pair_off(n, i) - base + (j - i - 1)];
         pair_grad<T>(q, p, a, b, (1 - c * a) * sj + c * q, c, gv, squared != 0, A, At, dcp);
       }
       sA[il * LD + lane] = A;
@@ -654,7 +655,7 @@ inline bool bad_curv(const void* c_raw, int c_mode, double c_min) {
 }
 // does [row_begin, row_end) hold a pair?  (the last row, [n - 1, n), holds none: its pair vector is empty and may be a null pointer)
 inline bool has_pairs(int64_t n, int64_t rb, int64_t re) {
-  return n <= kMaxNodes ? poff(n, re) > poff(n, rb) : re > rb;   // (beyond the node limit the product would overflow)
+  return n <= kMaxNodes ? pair_off(n, re) > pair_off(n, rb) : re > rb;   // (beyond the node limit the product would overflow)
 }
 inline int rows_of(size_t el) { return el == 4 ? 64 : 32; }
 inline size_t slab_bytes(size_t el, int64_t n, int m) {
@@ -775,12 +776,12 @@ __global__ __launch_bounds__(kC* kWaves) void product_fwd_kernel(PFactors<T> pf,
       sacc[il * kC + lane] = f ? sacc[il * kC + lane] + v : v;   // summed in factor order
     }
   }
-  const int64_t base = poff(n, rb);
+  const int64_t base = pair_off(n, rb);
   const bool interior = bj > bi && bj * kC + kC <= n;
   for (int r = 0; r < RW; ++r) {
     const int il = wave * RW + r, i = bi * kC + il;
     if (i < rb || i >= re) continue;
-    if (interior || (j > i && j < n)) out[poff(n, i) - base + (j - i - 1)] = sacc[il * kC + lane];
+    if (interior || (j > i && j < n)) out[pair_off(n, i) - base + (j - i - 1)] = sacc[il * kC + lane];
   }
 }
 
@@ -876,7 +877,7 @@ __device__ __forceinline__ void product_loss_tile(const PFactors<T>& pf, const T
     __syncthreads();
   }
   loss_resolve<T, LOSS>(la);
-  const int64_t base = poff(n, rb);
+  const int64_t base = pair_off(n, rb);
   size_t tcol = 0;                     // SUB: the lane's column of the dense matrix
   if constexpr (SUB) tcol = size_t(node_of(idx, min(j, n - 1), n_total));
   T lacc = 0;
@@ -888,7 +889,7 @@ __device__ __forceinline__ void product_loss_tile(const PFactors<T>& pf, const T
     if constexpr (SUB) {
       if (live) tg = target[size_t(node_of(idx, min(i, n - 1), n_total)) * size_t(n_total) + tcol];
     } else {
-      tg = live ? target[poff(n, i) - base + (j - i - 1)] : T(1);
+      tg = live ? target[pair_off(n, i) - base + (j - i - 1)] : T(1);
     }
     if constexpr (LOSS == MM_LOSS_NONE) {
       gr[r] = live ? tg : T(0);
@@ -1276,7 +1277,7 @@ int mm_stereo_pdist_bwd(int dtype, const void* x, const void* g, int64_t n, int 
   if (m > kMaxDim || n > kMaxNodes) return MM_ERR_UNSUPPORTED;
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (n < 2) {   // no pair: nothing but a zero curvature gradient
-    const hipError_t e = hipMemsetAsync(grad_c, 0, dtype == MM_F64 ? 8 : 4, st);
+    const hipError_t e = mm::clear_async(grad_c, dtype == MM_F64 ? 8 : 4, st);
     return e == hipSuccess ? MM_OK : int(e);
   }
   if (dtype == MM_F32)

@@ -19,6 +19,7 @@
 
 #include "../../include/mm_manifolds.h"
 #include "clear.hpp"
+#include "launch.hpp"
 #include "prof.hpp"
 #include "smallmat.hpp"
 #include "loss.hpp"
@@ -34,7 +35,6 @@ namespace mm {
 constexpr int kVBlock = 256;
 constexpr int kVecMaxDim = 64;
 constexpr int kVecSubMaxRows = 64;   // most rows per workgroup of the node-minibatch launch (their points sit in LDS)
-__host__ __device__ inline int64_t vpair_off(int64_t n, int64_t row) { return row * (2 * n - row - 1) / 2; }
 
 // (pair_q, load_point: vec_pair.hpp — shared with the bit-deterministic kernels of vec_det.hpp)
 
@@ -53,12 +53,12 @@ __global__ __launch_bounds__(kVBlock) void vec_pdist_fwd_kernel(const T* __restr
   const bool jin = j < n;
   T xj[MP];
   load_point<T, MP>(x, jin ? j : 0, m, xj);
-  const int64_t base = vpair_off(n, row_begin);
+  const int64_t base = pair_off(n, row_begin);
   for (int i = i0; i < i1; ++i) {
     T xi[MP];
     load_point<T, MP>(x, i, m, xi);  // wave-uniform -> scalar loads
     const T v = PairFn<T, KIND>::value(pair_q<T, KIND, MP>(xi, xj), squared);
-    if (jin && j > i) out[vpair_off(n, i) - base + (j - i - 1)] = v;
+    if (jin && j > i) out[pair_off(n, i) - base + (j - i - 1)] = v;
   }
 }
 
@@ -94,7 +94,7 @@ __global__ __launch_bounds__(kVBlock) void vec_pdist_bwd_kernel(const T* __restr
   T wsum = T(0), sp = T(1), loss_acc = T(0), ds_acc = T(0);
   loss_resolve<T, LOSS>(la);
   if constexpr (LOSS != MM_LOSS_NONE) sp = softplus_of(la.scale_raw);
-  const int64_t base = vpair_off(n, row_begin);
+  const int64_t base = pair_off(n, row_begin);
   // SUB: the tile's rows are staged in LDS — their node ids with one request, all their points with one more.  (Read in
   // the loop below, `x[idx[i] * m + k]` is two DEPENDENT scalar round trips per row: 47 us for the 130 816 pairs of a
   // 512-node Lorentz(24) batch; round 4.)
@@ -127,7 +127,7 @@ __global__ __launch_bounds__(kVBlock) void vec_pdist_bwd_kernel(const T* __restr
         const size_t in_ = size_t(rown[min(i, i1 - 1) - i0]);
         wv[u] = valid ? (up ? g[in_ * size_t(n_total) + size_t(jn)] : g[size_t(jn) * size_t(n_total) + in_]) : T(0);
       } else {
-        wv[u] = valid ? g[vpair_off(n, lo) - base + (hi - lo - 1)] : T(0);
+        wv[u] = valid ? g[pair_off(n, lo) - base + (hi - lo - 1)] : T(0);
       }
     }
 #pragma unroll
@@ -548,11 +548,6 @@ __global__ void vec_radam_multi_kernel(RadamMulti<T> s) {
 }
 
 // ------------------------------------------------------------------ launchers
-#define MMV_CHECK()                                    \
-  do {                                                 \
-    hipError_t e_ = hipGetLastError();                 \
-    if (e_ != hipSuccess) return static_cast<int>(e_); \
-  } while (0)
 
 template <typename T, int KIND, int MP>
 int vec_fwd_t(const T* x, int64_t n, int m, int64_t rb, int64_t re, int squared, T* out, hipStream_t st) {
@@ -568,7 +563,7 @@ int vec_fwd_t(const T* x, int64_t n, int m, int64_t rb, int64_t re, int squared,
     ProfScope prof(PROF_VEC_FWD, st);
     vec_pdist_fwd_kernel<T, KIND, MP><<<dim3(gx, gy), dim3(kVBlock), 0, st>>>(x, int(n), m, int(rb), int(re), squared, out, ti);
   }
-  MMV_CHECK();
+  MM_CHECK_LAUNCH();
   return MM_OK;
 }
 
@@ -609,11 +604,11 @@ int vec_bwd_t(const T* x, const T* g, int64_t n, int m, int64_t rb, int64_t re, 
           <<<dim3(int((n + kVBlock - 1) / kVBlock), int((n + TI - 1) / TI)), dim3(kVBlock), 0, st>>>(
               x, g, int(n), m, int(rb), int(re), squared, acc, la);
     }
-    MMV_CHECK();
+    MM_CHECK_LAUNCH();
   }
   vec_pdist_finalize_kernel<T, KIND, MP><<<dim3(int((n + 127) / 128)), dim3(128), 0, st>>>(
       x, acc, int(n), m, grad, LOSS != MM_LOSS_NONE ? slots : static_cast<T*>(nullptr), la.scale_raw, loss_out);
-  MMV_CHECK();
+  MM_CHECK_LAUNCH();
   return MM_OK;
 }
 
@@ -650,11 +645,11 @@ int vec_loss_subset_t(int loss_kind, const T* x, const T* dense, const T* scale_
     else
       vec_pdist_bwd_kernel<T, KIND, MP, TI, MM_LOSS_QUOTIENT, true><<<grid, dim3(kVBlock), 0, st>>>(
           x, dense, int(bs), m, int(rb), int(re), 1, acc, la, idx, int(n_total), rows);
-    MMV_CHECK();
+    MM_CHECK_LAUNCH();
   }
   vec_pdist_finalize_kernel<T, KIND, MP><<<dim3(int((n_total + 127) / 128)), dim3(128), 0, st>>>(
       x, acc, int(n_total), m, grad, slots, scale_raw, loss_out);
-  MMV_CHECK();
+  MM_CHECK_LAUNCH();
   return MM_OK;
 }
 
@@ -718,7 +713,7 @@ int vec_group_step_t(int optimizer, int count, const VecGroupParam* ps, hipStrea
   const dim3 grid(unsigned((most + 127) / 128), unsigned(count)), block(128);
   if (optimizer == MM_OPT_RADAM) vec_radam_multi_kernel<T><<<grid, block, 0, st>>>(s);
   else vec_rsgd_multi_kernel<T><<<grid, block, 0, st>>>(s.p);
-  MMV_CHECK();
+  MM_CHECK_LAUNCH();
   return MM_OK;
 }
 
@@ -820,7 +815,7 @@ int mm_vec_dist(int dtype, int kind, const void* x, const void* y, const void* g
     vec_dist_kernel<T, KIND><<<dim3(nb), dim3(128), 0, st>>>(static_cast<const T*>(x), static_cast<const T*>(y),
         static_cast<const T*>(g), cnt, m, squared, static_cast<T*>(out), static_cast<T*>(grad_x),
         static_cast<T*>(grad_y));
-    MMV_CHECK(); return MM_OK; }))
+    MM_CHECK_LAUNCH(); return MM_OK; }))
 }
 
 int mm_vec_map(int dtype, int kind, int op, const void* x, const void* u, const void* y, int64_t cnt, int m, void* out,
@@ -835,7 +830,7 @@ int mm_vec_map(int dtype, int kind, int op, const void* x, const void* u, const 
   MMV_DISPATCH_T(dtype, MMV_DISPATCH_KIND(kind, {
     vec_map_kernel<T, KIND><<<dim3(nb), dim3(128), 0, st>>>(op, static_cast<const T*>(x), static_cast<const T*>(u),
         static_cast<const T*>(y), cnt, m, static_cast<T*>(out));
-    MMV_CHECK(); return MM_OK; }))
+    MM_CHECK_LAUNCH(); return MM_OK; }))
 }
 
 int mm_vec_norm(int dtype, int kind, const void* u, int64_t cnt, int m, int squared, void* out, mm_stream_t stream) {
@@ -846,7 +841,7 @@ int mm_vec_norm(int dtype, int kind, const void* u, int64_t cnt, int m, int squa
   MMV_DISPATCH_T(dtype, MMV_DISPATCH_KIND(kind, {
     vec_norm_kernel<T, KIND><<<dim3(nb), dim3(128), 0, st>>>(static_cast<const T*>(u), cnt, m, squared,
         static_cast<T*>(out));
-    MMV_CHECK(); return MM_OK; }))
+    MM_CHECK_LAUNCH(); return MM_OK; }))
 }
 
 int mm_vec_rsgd_step(int dtype, int kind, const void* x, const void* egrad, int64_t cnt, int m, double lr,
@@ -864,7 +859,7 @@ int mm_vec_rsgd_step(int dtype, int kind, const void* x, const void* egrad, int6
   MMV_DISPATCH_T(dtype, MMV_DISPATCH_KIND(kind, {
     vec_rsgd_step_kernel<T, KIND><<<dim3(nb), dim3(128), 0, st>>>(static_cast<const T*>(x),
         static_cast<const T*>(egrad), cnt, m, T(lr), T(max_grad_norm), exact, static_cast<T*>(x_new));
-    MMV_CHECK(); return MM_OK; }))
+    MM_CHECK_LAUNCH(); return MM_OK; }))
 }
 
 int mm_vec_rsgd_momentum_step(int dtype, int kind, const void* x, const void* egrad, void* momentum_buffer, int64_t cnt,
@@ -884,7 +879,7 @@ int mm_vec_rsgd_momentum_step(int dtype, int kind, const void* x, const void* eg
     vec_rsgd_momentum_kernel<T, KIND><<<dim3(nb), dim3(128), 0, st>>>(static_cast<const T*>(x),
         static_cast<const T*>(egrad), static_cast<T*>(momentum_buffer), cnt, m, T(lr), T(momentum), T(dampening),
         T(max_grad_norm), exact, static_cast<T*>(x_new));
-    MMV_CHECK(); return MM_OK; }))
+    MM_CHECK_LAUNCH(); return MM_OK; }))
 }
 
 int mm_vec_radam_step(int dtype, int kind, const void* x, const void* egrad, void* exp_avg, void* exp_avg_sq,
@@ -906,7 +901,7 @@ int mm_vec_radam_step(int dtype, int kind, const void* x, const void* egrad, voi
     vec_radam_step_kernel<T, KIND><<<dim3(nb), dim3(128), 0, st>>>(static_cast<const T*>(x),
         static_cast<const T*>(egrad), static_cast<T*>(exp_avg), static_cast<T*>(exp_avg_sq), cnt, m, a,
         static_cast<T*>(x_new));
-    MMV_CHECK(); return MM_OK; }))
+    MM_CHECK_LAUNCH(); return MM_OK; }))
 }
 
 int mm_vec_radam_step_multi(int dtype, int count, const int* kinds, const void* const* xs, const void* const* egrads,

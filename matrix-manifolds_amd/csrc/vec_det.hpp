@@ -1,19 +1,12 @@
 // Vector-manifold pair gradients (Euclidean, Lorentz, sphere) WITHOUT float atomics: the bit-deterministic mode next to
-// vec_pdist_bwd_kernel (vec.hip), vec_pdist_bwd_sym_kernel (vec_sym.hpp) and the matrix-core forms (vec_gram.hip).
+// vec_pdist_bwd_kernel (vec.hip), vec_pdist_bwd_sym_kernel (vec_sym.hpp) and the matrix-core forms (vec_gram.hip).  The form, the
+// loss record and the determinism contract are det_common.hpp's; this file holds what is the vector manifolds' own.
 //
-// Form: BOTH ORDERS, COLUMN-OWNED — the ordered twin's.  A lane owns one column node j, keeps x_j, a[MP] and wsum in registers
-// and walks ONE chunk of rows i != j in ascending order; the row operand is wave-uniform (scalar loads; LDS staging for a node
-// minibatch).  Per pair the twin's arithmetic, unchanged: pair_q, PairFn::dq / ::value, loss_term, w, a[k] = fma(w, x_i[k], a[k]),
-// upstream gradients fetched UNR rows ahead.  A lane's chunk sums leave with plain stores into slab[chunk][entry][j] (coalesced
-// per entry; entries k < m, plus wsum for the Euclidean kind); the finalize kernel (one thread per node) adds a node's chunk
-// records in chunk order, applies the manifold map of vec_pdist_finalize_kernel and writes grad_x.  The loss term and
-// sum dloss/dm d^2 are counted in the i < j visit only, reduced per workgroup in a fixed order (butterfly inside a wavefront,
-// wavefronts in index order) and stored to ONE slot per workgroup; finalize adds the slots in fp64, lane t the slots t, t + 64,
-// ... in index order, the 64 lane sums through the same butterfly.
-//
-// Every order of summation is a pure function of (dtype, kind, n, m) (DetGeometry below): never of the row range, the device, an
-// occupancy query or the environment.  The four wavefronts of a workgroup own DIFFERENT columns (64 each) and walk the same
-// rows: nothing is folded through LDS but the loss record.  All offsets are 64-bit, as in the twin.
+// A lane keeps x_j, a[MP] and wsum in registers; the row operand is read with scalar loads (LDS staging for a node minibatch).
+// Per pair the ordered twin's arithmetic, unchanged: pair_q, PairFn::dq / ::value, loss_term, w, a[k] = fma(w, x_i[k], a[k]),
+// upstream gradients fetched UNR rows ahead.  A node's chunk record holds the entries k < m, plus wsum for the Euclidean kind; the
+// finalize kernel applies the manifold map of vec_pdist_finalize_kernel.  Every order of summation is a pure function of
+// (dtype, kind, n, m): geometry() below.  All offsets are 64-bit, as in the twin.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -21,6 +14,9 @@
 #include <cstdint>
 
 #include "../../include/mm_manifolds.h"
+#include "clear.hpp"
+#include "det_common.hpp"
+#include "launch.hpp"
 #include "smallmat.hpp"
 #include "loss.hpp"
 #include "vecfn.hpp"
@@ -29,12 +25,9 @@
 namespace mm {
 namespace vec_det {
 
-// ---- launch geometry: a pure function of (element size, kind, n, m) ----------------------------------------------------------
-constexpr int kWaves = 4;                        // wavefronts of a workgroup; each owns 64 columns of its own
-constexpr int kCols = 64 * kWaves;               // columns per workgroup
-constexpr int kMinRows = 8;                      // rows per chunk: a multiple of this (the unroll of the row walk), at least this
-constexpr int64_t kTargetWgs = 1024;             // the grid is sized towards this many workgroups (four per CU of an MI355X)
-constexpr size_t kSlabCap = size_t(64) << 20;    // the slab is at most max(one record per node, this)
+using det::DetGeometry;
+using det::kCols;
+using det::kWaves;
 constexpr int kStageRows = 64;                   // node minibatch: rows of a chunk staged in LDS at a time
 constexpr int kMaxDim = 64;                      // mm_vec_max_dim()
 constexpr int64_t kMaxNodes = int64_t(1) << 22;
@@ -42,28 +35,10 @@ constexpr int kNodeBlock = 128;                  // finalize: nodes per workgrou
 
 // entries of a node's chunk record: the m coefficient sums, and the sum of the weights where the map needs it
 constexpr int entries_of(int kind, int m) { return m + (kind == MM_EUCLIDEAN ? 1 : 0); }
-
-struct DetGeometry {
-  int64_t groups, chunks, rows;   // column groups, row chunks, rows per chunk: (chunks - 1) rows < n <= chunks rows
-  size_t slab_bytes, slot_bytes;
-  size_t bytes() const { return slab_bytes + slot_bytes; }
-};
+// rows per chunk: a multiple of det::kMinRows, the unroll of the row walk
 inline DetGeometry geometry(size_t esz, int kind, int64_t n, int m) {
-  DetGeometry g{};
-  if (n < 1) { g.groups = 0; g.chunks = 1; g.rows = kMinRows; g.slab_bytes = 0; g.slot_bytes = 0; return g; }
-  g.groups = (n + kCols - 1) / kCols;
-  int64_t want = (kTargetWgs + g.groups - 1) / g.groups;                     // falls as n grows
-  const size_t record = size_t(entries_of(kind, m)) * size_t(n) * esz;       // one chunk's records of all nodes
-  const int64_t cap = std::max<int64_t>(1, int64_t(kSlabCap / record));      // the slab stays within max(record, kSlabCap)
-  want = std::max<int64_t>(1, std::min(want, cap));
-  g.rows = std::max<int64_t>(kMinRows, ((n + want - 1) / want + kMinRows - 1) / kMinRows * kMinRows);
-  g.chunks = (n + g.rows - 1) / g.rows;
-  g.slab_bytes = (size_t(g.chunks) * record + 63) / 64 * 64;
-  g.slot_bytes = (2 * size_t(g.groups) * size_t(g.chunks) * esz + 63) / 64 * 64;
-  return g;
+  return det::geometry(esz, size_t(entries_of(kind, m)) * esz, n, det::kMinRows);
 }
-
-__host__ __device__ inline int64_t pair_off(int64_t n, int64_t row) { return row * (2 * n - row - 1) / 2; }   // mm_pair_offset
 
 // (node ids of a minibatch are clamped into the table: unvalidated caller data, as in the twin)
 __device__ __forceinline__ int batch_node(const int64_t* __restrict__ idx, int pos, int n_total) {
@@ -73,10 +48,9 @@ __device__ __forceinline__ int batch_node(const int64_t* __restrict__ idx, int p
 // ---- the pair kernel ------------------------------------------------------------------------------------------------------------
 // grid (groups, chunks); workgroup (x, y): columns [kCols x, kCols x + kCols), rows [rows y, rows y + rows) of ALL n rows.
 // A pair (i, j) is live iff i != j, j < n and row_begin <= min(i, j) < row_end; its upstream gradient / target sits at
-// pair_off(min) - base + (max - min - 1) of `g` (64-bit) — SUB: at dense[node(min)][node(max)], min / max by POSITION.  Rows that
-// hold no live pair for the columns are cut off the walk without moving a sum: a lane adds its live pairs in row order either way
-// (a dead pair adds w = 0).  slab [chunks][E][n], E = entries_of(KIND, m); slots [2][groups * chunks].  Every record and every
-// slot is written by every launch.  LOSS == MM_LOSS_NONE: `g` = upstream gradients, `squared` applies; else `g` = targets.
+// pair_off(min) - base + (max - min - 1) of `g` (64-bit) — SUB: at dense[node(min)][node(max)], min / max by POSITION.  A dead
+// pair adds w = 0.  slab [chunks][E][n], E = entries_of(KIND, m); slots [2][groups * chunks].  LOSS == MM_LOSS_NONE: `g` =
+// upstream gradients, `squared` applies; else `g` = targets.
 // SUB (a node minibatch): the n points of the launch are the nodes idx[0 .. n) of a table of n_total points; slab and slots are
 // addressed by batch POSITION, with the geometry of a full batch of n points.
 template <typename T, int KIND, int MP, int LOSS, bool SUB>
@@ -206,8 +180,7 @@ __global__ __launch_bounds__(kCols) void pair_kernel(const T* __restrict__ x, co
 // The node's chunk records added in chunk order, in T; then the manifold map of vec_pdist_finalize_kernel: 2 (x_j sum w -
 // sum w x_i) for the Euclidean kind, -J for Lorentz, identity for the sphere.  chunks == 0 (no pair launch): zero gradient, zero
 // loss record.  idx != null (a node minibatch): thread p owns batch position p and writes row idx[p] of the table's gradient —
-// ONE plain store per batch row, the rows outside the batch were cleared (clear_kernel) before the launch.  The first wavefront of block 0
-// closes the loss record (loss_finalize's conventions: {loss, dloss/dscale_raw = sigmoid(scale_raw) sum dloss/dm d^2}).
+// ONE plain store per batch row, the rows outside the batch were cleared (clear_async) before the launch.
 template <typename T, int KIND, int MP>
 __global__ __launch_bounds__(kNodeBlock) void finalize_kernel(const T* __restrict__ x, const T* __restrict__ slab, int n, int m, int chunks,
                                                                T* __restrict__ grad, const T* __restrict__ slots, int64_t nslots,
@@ -243,25 +216,7 @@ __global__ __launch_bounds__(kNodeBlock) void finalize_kernel(const T* __restric
   }
 }
 
-// ---- node minibatch: the table's gradient cleared to +0 before finalize stores the batch's rows -----------------------------------
-// (a kernel, not hipMemsetAsync: replayed from a captured graph, the memset node of this call left grad_x [200, 64] full of
-// foreign bytes on the SECOND replay on an MI355X — the loss record and the first replay were right.  The memset node IS the
-// cause: tests/test_replay_gpu.py reproduces it at nine other hipMemsetAsync sites of the library, at regions from 2.5 KB to
-// 52 KB, on every replay after the first and never eagerly, and each site is right once its memset is mm::clear_async (clear.hpp);
-// profiles/replay.md)
-template <typename T>
-__global__ __launch_bounds__(256) void clear_kernel(T* __restrict__ p, size_t count) {
-  const size_t t = size_t(blockIdx.x) * 256 + threadIdx.x;
-  if (t < count) p[t] = T(0);
-}
-
 // ---- launcher ----------------------------------------------------------------------------------------------------------------
-#define MM_VEC_DET_CHECK()                             \
-  do {                                                 \
-    hipError_t e_ = hipGetLastError();                 \
-    if (e_ != hipSuccess) return static_cast<int>(e_); \
-  } while (0)
-
 // loss_kind: MM_LOSS_NONE (g = upstream gradient, loss_out unused) / MM_LOSS_STRESS / MM_LOSS_QUOTIENT (g = targets; squared
 // distances).  !sub: a full batch of n points.  sub: a node minibatch (idx may be null only where it holds no pair): n = its size, x [n_total, m], g the dense
 // n_total x n_total target matrix, grad [n_total, m].
@@ -273,9 +228,8 @@ int run_t(int loss_kind, const T* x, const T* g, const T* scale_raw, int64_t n, 
   T* slab = static_cast<T*>(det_ws);
   T* slots = reinterpret_cast<T*>(static_cast<char*>(det_ws) + geo.slab_bytes);
   if (sub) {   // rows outside the batch: +0
-    const size_t count = size_t(n_total) * size_t(m);
-    clear_kernel<T><<<dim3(unsigned((count + 255) / 256)), dim3(256), 0, st>>>(grad, count);
-    MM_VEC_DET_CHECK();
+    const hipError_t e = clear_async(grad, size_t(n_total) * size_t(m) * sizeof(T), st);   // (a kernel, never a memset node: clear.hpp)
+    if (e != hipSuccess) return static_cast<int>(e);
   }
   int chunks = 0;
   int64_t nslots = 0;
@@ -294,7 +248,7 @@ int run_t(int loss_kind, const T* x, const T* g, const T* scale_raw, int64_t n, 
       else MM_VEC_DET_LAUNCH(MM_LOSS_NONE, false);
     }
 #undef MM_VEC_DET_LAUNCH
-    MM_VEC_DET_CHECK();
+    MM_CHECK_LAUNCH();
     chunks = int(geo.chunks);
     nslots = geo.groups * geo.chunks;
   }
@@ -303,7 +257,7 @@ int run_t(int loss_kind, const T* x, const T* g, const T* scale_raw, int64_t n, 
   finalize_kernel<T, KIND, MP><<<dim3(nb), dim3(kNodeBlock), 0, st>>>(x, slab, int(nf), m, chunks, grad, slots, nslots, scale_raw,
                                                                      loss_kind == MM_LOSS_NONE ? static_cast<T*>(nullptr) : loss_out,
                                                                      idx, int(n_total));
-  MM_VEC_DET_CHECK();
+  MM_CHECK_LAUNCH();
   return MM_OK;
 }
 

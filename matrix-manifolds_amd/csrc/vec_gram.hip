@@ -19,6 +19,7 @@
 
 #include "../../include/mm_manifolds.h"
 #include "clear.hpp"
+#include "launch.hpp"
 #include "prof.hpp"
 #include "stamp.hpp"
 #include "smallmat.hpp"
@@ -29,8 +30,6 @@ namespace mm {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef double f64x4 __attribute__((ext_vector_type(4)));
-
-__host__ __device__ inline int64_t gpair_off(int64_t n, int64_t row) { return row * (2 * n - row - 1) / 2; }
 
 template <typename T> __device__ __forceinline__ T gacos(T c);
 template <> __device__ __forceinline__ float gacos<float>(float c) { return ::acosf(c); }
@@ -106,7 +105,7 @@ __global__ __launch_bounds__(64 * kGramWaves) void vec_gram_fwd_f32_kernel(const
     if (KIND == MM_LORENTZ && k != 0) a = -a;
     av[s] = a;
   }
-  const int64_t base = gpair_off(n, row_begin);
+  const int64_t base = pair_off(n, row_begin);
   MM_FSTAMP(1);
   for (int t = 0; t < kGramFwdTiles; ++t) {
     const int j0 = (jt0 + t) * 32;
@@ -143,7 +142,7 @@ __global__ __launch_bounds__(64 * kGramWaves) void vec_gram_fwd_f32_kernel(const
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
       const int c4 = 4 * (lane & 7);
       int row = i0 + (lane >> 3);
-      int64_t o = gpair_off(n, row) - base + (j0 + c4 - row - 1);
+      int64_t o = pair_off(n, row) - base + (j0 + c4 - row - 1);
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         const f32x4u v = *reinterpret_cast<const f32x4u*>(&sO[wave][(lane >> 3) + 8 * k][c4]);
@@ -156,7 +155,7 @@ __global__ __launch_bounds__(64 * kGramWaves) void vec_gram_fwd_f32_kernel(const
       // offsets advance by additions: rows in register order are i0 + 4h + {0,1,2,3, 8,...}, and
       // off(row + 1) = off(row) + n - row - 2 (a 64-bit multiply per element cost more than the acosh)
       int row = i0 + 4 * h;
-      int64_t o = gpair_off(n, row) - base + (j - row - 1);
+      int64_t o = pair_off(n, row) - base + (j - row - 1);
 #pragma unroll
       for (int q = 0; q < 16; ++q) {
         const float v = gram_value<float, KIND>(acc[q], squared);
@@ -200,16 +199,15 @@ __global__ __launch_bounds__(64 * kGramWaves) void vec_gram_fwd_f64_kernel(const
     if (KIND == MM_LORENTZ && k != 0) a = -a;
     acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0);
   }
-  const int64_t base = gpair_off(n, row_begin);
+  const int64_t base = pair_off(n, row_begin);
   const int j = j0 + r;
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     const int i = i0 + h + 4 * q;  // f64 C/D map: row = (lane>>4) + 4*reg
     const double v = gram_value<double, KIND>(acc[q], squared);
-    if (i < row_end && j < n && j > i) out[gpair_off(n, i) - base + (j - i - 1)] = v;
+    if (i < row_end && j < n && j > i) out[pair_off(n, i) - base + (j - i - 1)] = v;
   }
 }
-
 
 // ------------------------------------------------------------------ backward on the matrix cores
 // grad_j = sum_i w_ij * (d q_ij / d x_j) with w_ij = g_ij * dout/dq(q_ij): with W the (symmetric, zero-
@@ -277,8 +275,8 @@ void vec_gram_bwd_f32_kernel(const float* __restrict__ x, const float* __restric
   loss_resolve<float, LOSS>(la);
   if constexpr (LOSS != MM_LOSS_NONE) sp = softplus_of(la.scale_raw);
   const float kInvalid = LOSS != MM_LOSS_NONE ? __builtin_nanf("") : 0.f;
-  const u32 base = u32(gpair_off(n, row_begin));
-  const u32 gmax = u32(gpair_off(n, row_end)) - base - 1u;  // last valid index of this shard's slice
+  const u32 base = u32(pair_off(n, row_begin));
+  const u32 gmax = u32(pair_off(n, row_end)) - base - 1u;  // last valid index of this shard's slice
   auto goff = [&](int lo, int hi) -> u32 {  // pair (lo < hi) -> offset in this shard's slice, clamped
     const u32 o = u32(lo) * u32(2 * n - lo - 1) / 2u - base + u32(hi - lo - 1);
     return o > gmax ? gmax : o;   // (also catches the wrap-around of rows below row_begin)
@@ -458,7 +456,6 @@ void vec_gram_bwd_f32_kernel(const float* __restrict__ x, const float* __restric
   }
 }
 
-
 // ------------------------------------------------------------------ backward, symmetric tiles (fp32)
 // Every UNORDERED 32 x 32 tile of the pair matrix is visited once: its W = g * dout/dq(Q) feeds BOTH gradient
 // blocks, ACC_J += W^T X_I (the accumulator is the A operand as it lies, as above) and ACC_I += W X_J (W turned
@@ -509,8 +506,8 @@ void vec_gram_bwd_sym_f32_kernel(const float* __restrict__ x, const float* __res
   const int rc = r < m ? r : m - 1;
   const int jb = Bs * 4 + wave, J = jb * 32;   // this wavefront's column block
   const bool j_live = jb < nT;                  // (ragged last super-tile)
-  const u32 base = u32(gpair_off(n, row_begin));
-  const u32 gmax = u32(gpair_off(n, row_end)) - base - 1u;  // last valid index of this shard's slice
+  const u32 base = u32(pair_off(n, row_begin));
+  const u32 gmax = u32(pair_off(n, row_end)) - base - 1u;  // last valid index of this shard's slice
   // Upstream gradients (accumulator layout) and the Gram A operand (rows of X_I) of step t.  Issued ONE STEP AHEAD into a
   // second register set (the first request before the prologue's barrier): a wavefront spent a quarter of its life
   // waiting for these loads at the top of every step (tools/gram_timeline.py).  Unconditional, from clamped offsets: for a
@@ -897,7 +894,7 @@ int vec_gram_bwd_launch(int kind, int loss_kind, const float* xp, const float* g
 int vec_gram_bwd_launch(int kind, int loss_kind, const double* xp, const double* gp, int64_t n, int m,
                         int64_t row_begin, int64_t row_end, int squared, double* op, LossArgs<double> la,
                         hipStream_t st) {
-  hipError_t e = hipMemsetAsync(op, 0, sizeof(double) * size_t(n) * m, st);
+  hipError_t e = clear_async(op, sizeof(double) * size_t(n) * m, st);
   if (e != hipSuccess) return int(e);
   if (mm_pair_offset(n, row_end) == mm_pair_offset(n, row_begin)) return MM_OK;
   const int nT = int((n + 15) / 16);
@@ -948,7 +945,7 @@ template <typename T>
 int vec_gram_loss_t(int kind, int loss_kind, const T* x, const T* target, const T* scale_raw, int64_t n, int m,
                     int64_t row_begin, int64_t row_end, double alpha, double eps, int terms, const double* loss_params, T* loss_out, T* grad,
                     T* slots, hipStream_t st) {
-  hipError_t e = hipMemsetAsync(slots, 0, sizeof(T) * 2 * kLossSlots, st);
+  hipError_t e = clear_async(slots, sizeof(T) * 2 * kLossSlots, st);
   if (e != hipSuccess) return int(e);
   LossArgs<T> la{scale_raw, T(alpha), T(eps), terms, slots, loss_params};
   const int rc = vec_gram_bwd_launch(kind, loss_kind, x, target, n, m, row_begin, row_end, 1, grad, la, st);

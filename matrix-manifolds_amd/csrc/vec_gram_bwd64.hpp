@@ -40,8 +40,8 @@ __global__ __launch_bounds__(64 * kGramBwdWaves) void vec_gram_bwd_f64_kernel(co
   loss_resolve<double, LOSS>(la);
   if constexpr (LOSS != MM_LOSS_NONE) sp = softplus_of(la.scale_raw);
   const double kInvalid = LOSS != MM_LOSS_NONE ? __builtin_nan("") : 0.0;
-  const u32 base = u32(gpair_off(n, row_begin));
-  const u32 gmax = u32(gpair_off(n, row_end)) - base - 1u;
+  const u32 base = u32(pair_off(n, row_begin));
+  const u32 gmax = u32(pair_off(n, row_end)) - base - 1u;
   auto goff = [&](int lo, int hi) -> u32 {  // pair (lo < hi) -> offset in this shard's slice, clamped
     const u32 o = u32(lo) * u32(2 * n - lo - 1) / 2u - base + u32(hi - lo - 1);
     return o > gmax ? gmax : o;

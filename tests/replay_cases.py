@@ -16,7 +16,7 @@ A row names
     minibatch, outside       True: rows of the gradient outside the batch are checked, and (what, the header line that promises it):
                              PLUS_ZERO = every bit zero, in every family
     cleared                  None, or (formula, bytes) of the region the call clears before it accumulates, for the rows whose
-                             cleared region is at least HAZARD_BYTES — the size of the recorded failure (csrc/vec_det.hpp,
+                             cleared region is at least HAZARD_BYTES — the size of the recorded failure (csrc/clear.hpp,
                              profiles/vec_deterministic.md: grad_x [200, 64] fp32 = 51 200 bytes)
     same_points              None, or why A and B share the points (the module provides one draw of them)
     one_side                 None, or why A and B share the target / upstream vector (the module provides one)
@@ -141,7 +141,7 @@ def _vec_rows():
         cleared = None
         if large:
             esz = ESZ[dname]
-            if det:      # vec_det::clear_kernel over grad_x [n_total, m]
+            if det:      # clear_async over grad_x [n_total, m]
                 cleared = ('n_total * m * sizeof(T)', vc.N_TABLE * m * esz)
             else:        # csrc/vec.hip, vec_loss_subset_t: the accumulators of all nodes (the loss slots behind them not counted)
                 cleared = ('n_total * (pad_dim(m) + 1) * sizeof(T)', vc.N_TABLE * (vc.pad_dim(m) + 1) * esz)
@@ -155,7 +155,8 @@ def _vec_rows():
         for short in ('bwd', 'loss', 'subset'):
             for det in (False, True):
                 add(short, det, dname, VEC_KIND, VEC_M)
-    add('bwd_gram', False, 'f32', VEC_KIND, VEC_M)          # (the matrix-core backward is fp32 only)
+    add('bwd_gram', False, 'f32', VEC_KIND, VEC_M)
+    add('bwd_gram', False, 'f64', VEC_KIND, VEC_M)          # (clears grad_x [n, m] at the head of the call: 131 * 11 * 8 bytes)
     for det in (False, True):
         add('subset', det, 'f32', *VEC_LARGE, large=True)
     # another path of the two full-batch atomic entries: fp32 beyond m = 32 the symmetric pair kernel is not built and the ordered
