@@ -904,6 +904,49 @@ size_t mm_graph_sort_rows_ws_bytes(int dtype, int64_t n);
 int mm_graph_sort_rows(int dtype, const void* dist, int64_t n, int* order, void* ws, size_t ws_bytes,
                        mm_stream_t stream);
 
+/* ---- all-pairs graph distances (csrc/graph_paths.hip) ----------------------------- */
+/* What data/graph.py:15-87 (targets) and pyx/impl/precision.cpp:44-92 (the evaluator's shortest-path trees) compute before
+ * the first step.  The graph is a CSR adjacency in device memory, int32: row v of indptr / indices lists the OUT-neighbours
+ * of v (metrics.graph_csr); self-loops and repeated neighbours are allowed and change nothing, neighbour ids outside
+ * [0, n) are skipped.  Everywhere dist [n,n] int32 holds dist[v][s] = d(v -> s), 0 on the diagonal and -1 where s cannot
+ * be reached from v; n <= mm_graph_max_nodes() = 46340 (n * n < 2^31, as mm_graph_sort_rows).  The entries issue kernel
+ * launches only — no allocation, no synchronisation, no memset node — and check their arguments before anything touches
+ * the GPU (MM_ERR_ARG); n == 0 does nothing.
+ *
+ * mm_graph_hops: hop distances of an unweighted graph, directed or not, every source at once with one BIT per source:
+ * R_L[v] = {s : d(v -> s) <= L} = R_{L-1}[v] u U_{u in N(v)} R_{L-1}[u], one launch per level.  The call issues the levels
+ * level_begin + 1 ... level_begin + level_count.  level_begin == 0 first initialises ws and dist (identity bits; 0 on the
+ * diagonal, -1 elsewhere): both may hold anything on entry.  level_begin == k > 0 continues from the state that the call
+ * which issued level k left in ws and dist.  new_bits int32[level_count] (device) is cleared and written by the call:
+ * new_bits[j] = 1 if level level_begin + j + 1 found a new pair (v, s), else 0 — the caller reads it whenever it likes and
+ * decides when to stop; the hop diameter is the last level whose flag is 1.  Levels issued after the frontier has emptied
+ * change nothing.  ws: mm_graph_hops_ws_bytes(n) bytes, 8-byte aligned — three bit matrices [n][ceil(n / 64)] of 64-bit
+ * words (reached, and two frontiers used alternately); 0 for n outside [0, mm_graph_max_nodes()].
+ * MM_ERR_ARG: n < 0 or n > mm_graph_max_nodes(), level_begin < 0, level_count < 1, level_begin + level_count >= 2^31, and
+ * for n > 0 a null pointer, ws_bytes too small or ws not 8-byte aligned. */
+int64_t mm_graph_max_nodes(void);
+size_t mm_graph_hops_ws_bytes(int64_t n);
+int mm_graph_hops(const int* indptr, const int* indices, int64_t n, int level_begin, int level_count, int* dist,
+                  int* new_bits, void* ws, size_t ws_bytes, mm_stream_t stream);
+
+/* Cost distances: costs int32[nnz] (device) holds the cost of edge indices[e]; of parallel edges the cheapest counts.
+ * Blocked Floyd-Warshall over (min, +) in int32 on dist itself: 3 ceil(n / 64) + 3 launches (4 for n <= 64), a function of n alone, so the
+ * call is asynchronous end to end.  dist may hold anything on entry.  PRECONDITION (not checked on the device; the Python
+ * layer checks it on the host graph): costs are integers >= 0 and (n - 1) * max cost < 2^30 - 1, the in-kernel sentinel for
+ * "no route" — every finite distance then stays below it and no sum of two entries overflows.
+ * MM_ERR_ARG: n < 0 or n > mm_graph_max_nodes(), a null pointer with n > 0. */
+int mm_graph_cost_paths(const int* indptr, const int* indices, const int* costs, int64_t n, int* dist, mm_stream_t stream);
+
+/* The targets of GraphDataset (data/dataset.py:16-19) straight from dist: over the upper triangle (i < j, pair-vector order,
+ * pair (i, j) at mm_pair_offset(n, i) + j - i - 1) the value T(d) * T(d) / (T(dmax) * T(dmax)), T = float (MM_F32) or double
+ * (MM_F64), one correctly rounded multiply and one correctly rounded divide per element, written as the condensed vector
+ * [n(n-1)/2] and / or the dense symmetric matrix [n,n] with zero diagonal (either may be NULL).  stats int64[2] (device,
+ * 8-byte aligned, cleared by the call): the largest finite distance of the upper triangle — dmax, read by the scaling kernel
+ * from device memory: no host round trip — and its number of -1 entries.  A -1 yields +inf in the outputs.
+ * MM_ERR_ARG: an unknown dtype, n < 0 or n > mm_graph_max_nodes(), a null or misaligned stats, a null dist with n > 0. */
+int mm_graph_targets(int dtype, const int* dist, int64_t n, int64_t* stats, void* condensed, void* dense,
+                     mm_stream_t stream);
+
 /* ---- the collective of the sharded path ----------------------------------------- */
 /* One process per GPU; the embedding is replicated, the pair list is cut into row ranges (mm_shard_rows) and every
  * step ends with ONE all-reduce(sum) of {point gradients, loss, scale gradients} over a process-lifetime RCCL

@@ -5,6 +5,7 @@ The full-batch step and the multi-GPU shards only ever need the condensed pair v
 row-major upper-triangle order as `Manifold.pdist`), so that is what is stored; the dense n x n
 matrix the reference keeps is built on first use by a node mini-batch (`dataset[indices]`,
 train.py:203-213) and cached."""
+import numpy as np
 import torch
 from torch.utils.data import Dataset
 
@@ -17,6 +18,39 @@ class GraphDataset(Dataset):
         sq = pdists.pow(2)
         self.condensed = sq / sq.max()     # (P,)
         self._dense = None                 # (n, n), lazily
+
+    @classmethod
+    def from_graph(cls, g, device=None, dtype=None):
+        """The targets of a networkx graph (hop distances) without the host detour: on a cuda device the distance matrix
+        (`graph_distances`) and `condensed` (mm_graph_targets: max-normalised squares in pair-vector order) are computed there —
+        no n x n float64 host matrix, no upload.  On the CPU it is GraphDataset(compute_graph_pdists(g)).  A disconnected
+        graph raises ValueError."""
+        from graphembed.data.graph import compute_graph_pdists, gpu_apsp_enabled, graph_distances
+        dtype = dtype or torch.get_default_dtype()
+        if device is None:
+            device = 'cuda' if gpu_apsp_enabled() else 'cpu'
+        device = torch.device(device)
+        if device.type != 'cuda' or not gpu_apsp_enabled():
+            pd = compute_graph_pdists(g)
+            if not np.isfinite(pd).all():
+                raise ValueError('GraphDataset needs a connected graph')
+            return cls(torch.from_numpy(pd).to(dtype).to(device))
+        from graphembed import _backend as B
+        if dtype not in (torch.float32, torch.float64):
+            raise TypeError(f'matrix-manifolds_amd kernels exist for float32/float64, got {dtype}')
+        dist = graph_distances(g, device)
+        n = dist.shape[0]
+        with B.on_device(device):
+            stats = torch.empty(2, dtype=torch.int64, device=device)
+            condensed = torch.empty(n * (n - 1) // 2, dtype=dtype, device=device)
+            B.lib().call('mm_graph_targets', B.dtype_code(condensed), B.ptr(dist), n, B.ptr(stats), B.ptr(condensed), None,
+                         B.stream_of(dist))
+        if int(stats[1].item()) != 0:
+            raise ValueError('GraphDataset needs a connected graph')
+        self = cls.__new__(cls)
+        self.condensed = condensed
+        self._dense = None
+        return self
 
     @property
     def pdists(self):

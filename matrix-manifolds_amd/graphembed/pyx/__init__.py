@@ -4,11 +4,14 @@ shortest-path tree) is prepared once and uploaded; the mean average precision an
 statistics counted on the GPU (csrc/metrics.hip), the row sort they walk is rocPRIM's segmented radix sort
 (csrc/metrics_sort.hip).  Unweighted graphs (BFS layers) and weighted graphs — integer edge costs under the edge
 attribute `weight`, as precision.pyx:117-121 detects them — whose layers are the dense ranks of the Dijkstra distances
-(precision.cpp:76-92, 150-166)."""
+(precision.cpp:76-92, 150-166).  On a cuda device the graph distances themselves come from `graph_distances`
+(csrc/graph_paths.hip): the hop matrix of an unweighted graph is the layer matrix and stays on the device; a weighted
+graph's matrix is copied to the host once and ranked there.  MM_GRAPH_APSP=scipy keeps scipy's BFS / Dijkstra."""
 import numpy as np
 import torch
 
 from graphembed import _backend as B
+from graphembed.data.graph import gpu_apsp_enabled, graph_distances
 from graphembed.metrics import graph_csr, node_average_precision
 from graphembed.utils import squareform1
 
@@ -36,10 +39,23 @@ class FastPrecision:
         self.indptr, self.indices = graph_csr(g, self.device)
         edges = list(g.edges(data=True))
         self.weighted = bool(edges) and 'weight' in edges[0][2]      # precision.pyx:117-121
+        on_gpu = self.device.type == 'cuda' and gpu_apsp_enabled()   # distances by csrc/graph_paths.hip (MM_GRAPH_APSP=scipy: below)
         if self.weighted:
             adj = nx.to_scipy_sparse_array(g, nodelist=range(self.n), weight='weight')
             if not np.all(np.equal(np.mod(adj.data, 1), 0)):
                 raise ValueError('weighted graphs need integer edge costs (the reference stores them as int)')
+        if on_gpu:
+            dist = graph_distances(g, self.device, weight='weight' if self.weighted else None)
+            if bool((dist < 0).any()):
+                raise ValueError('FastPrecision needs a connected graph')
+            if not self.weighted:   # the hop matrix is the layer matrix and never leaves the device
+                self.hops = dist.contiguous()
+                self.num_layers = int(dist.max()) + 1
+                self._nodes_per_layer = torch.bincount(dist.reshape(-1), minlength=self.num_layers).cpu().numpy()
+                self._sort_ws = None
+                return
+            dist = dist.cpu().numpy()   # one copy; ranking the distances into layers stays on the host (tree_layers)
+        elif self.weighted:
             dist = shortest_path(adj, method='D', unweighted=False, directed=g.is_directed())
         else:
             adj = nx.to_scipy_sparse_array(g, nodelist=range(self.n))
