@@ -880,7 +880,11 @@ int mm_pair_gather(int dtype, const void* dense, int64_t n, const int64_t* idx, 
  *   dist          [n,n] dense symmetric embedding distances (zeros on the diagonal)
  *   indptr/indices  CSR adjacency of the (unweighted) graph, int32, device memory
  *   rank_scratch  int[nnz] device scratch
- *   ap_out        [n]: AP(u) = 1/deg(u) sum_{v in N(u)} (#neighbours ranked <= v) / rank(v); ties by node index. */
+ *   ap_out        [n]: AP(u) = 1/deg(u) sum_{v in N(u)} (#neighbours ranked <= v) / rank(v); 0 for a node of degree 0.
+ * THE ORDER (the contract of this entry and of mm_graph_sort_rows): one total order on (distance, node) — numbers
+ * ascending with -0.0 == +0.0, then every NaN of either sign and any payload, ties by node index.  It is the order of
+ * numpy.argsort(kind='stable') and torch.sort(stable=True).  rank(v) is the position of v in that order of row u with u
+ * itself removed (1 = closest), so the ranks of a row are distinct; on return rank_scratch[e] holds rank(indices[e]). */
 int mm_graph_average_precision(int dtype, const void* dist, int64_t n, const int* indptr,
                                const int* indices, int* rank_scratch, void* ap_out,
                                mm_stream_t stream);
@@ -899,7 +903,10 @@ int mm_graph_layer_f1(const int* order, const int* hops, int64_t n, const int* i
 
 /* Row-wise stable argsort of the dense embedding-distance matrix: order[u][k] = the node with the k-th smallest
  * distance to u, ties in node order (SortNodeDists, pyx/impl/precision.cpp:107-121) — the input of mm_graph_layer_f1.
- * dist [n,n] (device), order int32 [n,n], ws of mm_graph_sort_rows_ws_bytes bytes; n <= 46340. */
+ * The order is the total order stated at mm_graph_average_precision: numbers ascending with -0.0 == +0.0, then every NaN
+ * of either sign, ties by node index (the keys are copied into ws with every NaN made the one canonical NaN; dist is
+ * only read).  dist [n,n] (device), order int32 [n,n], ws of mm_graph_sort_rows_ws_bytes bytes; n <= 46340: a larger n
+ * makes mm_graph_sort_rows_ws_bytes return 0 and mm_graph_sort_rows MM_ERR_UNSUPPORTED, before anything is launched. */
 size_t mm_graph_sort_rows_ws_bytes(int dtype, int64_t n);
 int mm_graph_sort_rows(int dtype, const void* dist, int64_t n, int* order, void* ws, size_t ws_bytes,
                        mm_stream_t stream);

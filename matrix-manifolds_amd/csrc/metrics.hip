@@ -11,6 +11,11 @@
 // i.e. a stable argsort), then the neighbours' ranks are ranked among themselves.  Cost 2|E| n comparisons
 // against the n^2 log n of sorting every row; rows of the dense distance matrix are read coalesced and stay
 // in L2 for the deg(u) passes.
+//
+// The order (the contract of mm_graph_average_precision and mm_graph_sort_rows, include/mm_manifolds.h): one total
+// order on (distance, node) — numbers ascending with -0.0 == +0.0, then every NaN of either sign, ties by node index;
+// what numpy.argsort(kind='stable') and torch.sort(stable=True) give.  Ranks are therefore distinct, and a row of
+// NaN distances (a diverged embedding) ranks its nodes by index instead of giving every neighbour rank 1.
 #include <hip/hip_runtime.h>
 
 #include "../../include/mm_manifolds.h"
@@ -35,10 +40,14 @@ __global__ __launch_bounds__(kApBlock) void average_precision_kernel(const T* __
   for (int e = e0; e < e1; ++e) {  // block-uniform
     const int v = indices[e];
     const T dv = row[v];
+    const bool v_nan = dv != dv;  // block-uniform
     int c = 0;
     for (int w = threadIdx.x; w < n; w += kApBlock) {
       const T dw = row[w];
-      c += (w != u && w != v && (dw < dv || (dw == dv && w < v))) ? 1 : 0;
+      // w stands in front of v in the total order: a number in front of every NaN, NaN ties NaN, -0 ties +0
+      const bool tie = v_nan ? dw != dw : dw == dv;
+      const bool closer = dw < dv || (v_nan && dw == dw) || (tie && w < v);
+      c += (w != u && closer) ? 1 : 0;  // (w == v: tie, and v < v is false)
     }
     c = wave_sum(c);
     if (lane == 0) part[wave] = c;

@@ -2,8 +2,15 @@
 // FastPrecision::LayerF1Scores (graphembed/graphembed/pyx/impl/precision.cpp:107-121, SortNodeDists; ties keep
 // node order, as the evaluator's walk of tied distances is defined by it).  rocPRIM's segmented radix sort (one segment
 // per row, LSD radix = stable) on (distance, node) pairs; the library call replaces the framework sort the evaluator
-// used in round 1.  Everything lives in the caller's workspace:
-//   [keys_out n^2][values_in n^2 int][offsets n+1 int][rocPRIM temporary storage]
+// used in round 1.
+//
+// The order is the contract of include/mm_manifolds.h: numbers ascending with -0.0 == +0.0, then every NaN of either
+// sign, ties by node index.  rocPRIM's key codec orders floats by their bits (sign-magnitude flipped): it folds -0.0
+// into +0.0, but a NaN with the sign bit set would sort in front of -inf and two NaNs with different payloads by payload
+// instead of by node.  So the keys are copied into the workspace with every NaN replaced by the one canonical quiet NaN
+// (sign clear: behind +inf) in the pass that writes the node ids, and the sort reads that copy.
+// Everything lives in the caller's workspace:
+//   [keys_in n^2][keys_out n^2][values_in n^2 int][offsets n+1 int][rocPRIM temporary storage]
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -14,10 +21,16 @@
 namespace mm {
 namespace {
 
-__global__ void sort_iota_kernel(int* __restrict__ values, int* __restrict__ offsets, int n) {
+template <typename T>
+__global__ void sort_prepare_kernel(const T* __restrict__ dist, T* __restrict__ keys, int* __restrict__ values,
+                                    int* __restrict__ offsets, int n) {
   const int64_t t = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
   const int64_t total = int64_t(n) * n;
-  if (t < total) values[t] = int(t % n);
+  if (t < total) {
+    const T d = dist[t];
+    keys[t] = d != d ? T(__builtin_nanf("")) : d;  // one NaN: +quiet, whatever the sign and payload that came in
+    values[t] = int(t % n);
+  }
   if (t <= n) offsets[t] = int(t * n);
 }
 
@@ -35,7 +48,7 @@ template <typename T> size_t sort_temp_bytes(int64_t n) {
 
 template <typename T> size_t sort_ws_bytes(int64_t n) {
   const size_t nn = size_t(n) * n;
-  return align_up(nn * sizeof(T)) + align_up(nn * sizeof(int)) + align_up((n + 1) * sizeof(int)) + align_up(sort_temp_bytes<T>(n));
+  return 2 * align_up(nn * sizeof(T)) + align_up(nn * sizeof(int)) + align_up((n + 1) * sizeof(int)) + align_up(sort_temp_bytes<T>(n));
 }
 
 template <typename T>
@@ -43,14 +56,15 @@ int sort_rows(const T* dist, int64_t n, int* order, void* ws, size_t ws_bytes, h
   if (ws_bytes < sort_ws_bytes<T>(n)) return MM_ERR_ARG;
   const size_t nn = size_t(n) * n;
   char* p = static_cast<char*>(ws);
+  T* keys_in = reinterpret_cast<T*>(p); p += align_up(nn * sizeof(T));
   T* keys_out = reinterpret_cast<T*>(p); p += align_up(nn * sizeof(T));
   int* values_in = reinterpret_cast<int*>(p); p += align_up(nn * sizeof(int));
   int* offsets = reinterpret_cast<int*>(p); p += align_up((n + 1) * sizeof(int));
   size_t temp = sort_temp_bytes<T>(n);
-  sort_iota_kernel<<<dim3(unsigned((nn + 255) / 256)), dim3(256), 0, st>>>(values_in, offsets, int(n));
+  sort_prepare_kernel<T><<<dim3(unsigned((nn + 255) / 256)), dim3(256), 0, st>>>(dist, keys_in, values_in, offsets, int(n));
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return int(e);
-  e = rocprim::segmented_radix_sort_pairs(p, temp, dist, keys_out, values_in, order, unsigned(nn), unsigned(n), offsets,
+  e = rocprim::segmented_radix_sort_pairs(p, temp, keys_in, keys_out, values_in, order, unsigned(nn), unsigned(n), offsets,
                                           offsets + 1, 0, unsigned(8 * sizeof(T)), st);
   return e == hipSuccess ? MM_OK : int(e);
 }
