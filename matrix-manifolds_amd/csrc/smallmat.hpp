@@ -1536,6 +1536,35 @@ template <int N> __device__ __forceinline__ int reduce_slot(int lane, bool& writ
   return idx;
 }
 
+// ---- transposing reduction, lane-group form: N <= 16 values per lane -> ONE total per lane over its 16-LANE GROUP --------
+// The levels of lane bits 3..0 only (row_ror:8, row_half_mirror, two quad_perm): no v_permlane*_swap, which issues like 3.1
+// plain instructions against 1.6 for an add with DPP (tools/micro/xlane_rate.hip) and overwrites both its operands.  The four
+// groups of a wavefront end up with four partial totals of every value; whoever consumes them adds the four (the SPD
+// backward: four planes of its LDS staging buffer, added when a segment's row sums leave — spd_pair.hpp).  6 values:
+// 9 + 4 + 3 + 1 = 17 instructions, none of them a swap; 10 values: 15 + 7 + 4 + 1 = 27; 3 values: 4 + 3 + 1 + 1 = 9.
+template <int N, typename T> __device__ __forceinline__ T group_reduce_transposed(const T (&v)[N], int lane) {
+  static_assert(N >= 1 && N <= 16, "16 lanes hold at most 16 values");
+  return wave_reduce_level<2, N, T>(v, lane);
+}
+// Index of the value `group_reduce_transposed<N>` leaves in `lane` (a function of lane & 15: the same in all four groups);
+// writer = false for lanes that hold a duplicate (every value has exactly one writer lane PER GROUP).
+template <int N> __host__ __device__ __forceinline__ int group_reduce_slot(int lane, bool& writer) {
+  int cnt[5];
+  cnt[0] = N;
+#pragma unroll
+  for (int l = 0; l < 4; ++l) cnt[l + 1] = (cnt[l] + 1) / 2;
+  int idx = 0;
+  writer = true;
+#pragma unroll
+  for (int l = 3; l >= 0; --l) {
+    const int n = cnt[l], m = cnt[l + 1];
+    const int bit = (lane >> (3 - l)) & 1;
+    if ((n & 1) && idx == m - 1) { idx = n - 1; writer = writer && !bit; }   // came through a butterfly
+    else idx = 2 * idx + bit;
+  }
+  return idx;
+}
+
 template <typename T> __device__ __forceinline__ T wave_sum(T x) {
 #pragma unroll
   for (int m = 32; m >= 1; m >>= 1) x += __shfl_xor(x, m, 64);

@@ -540,7 +540,13 @@ __global__ __launch_bounds__((64 * bwd_waves<T, D>()), (bwd_min_waves_nc<T, D, N
   // and leave with ONE set of atomics per column block (float atomics are a per-CU serial resource, ~50 ns per
   // wave instruction).
   static_assert(TI % 2 == 0, "the row loop is unrolled twice");
-  __shared__ T redM[NW][TI][NP];
+  // Row sums, SPD(2 .. 4): the lane-group reduction (smallmat.hpp, group_reduce_transposed: DPP levels only) leaves one partial
+  // total per 16-lane group, each group stages its own plane and the segment flush adds the planes.  No measured instantiation
+  // lost against the whole-wavefront form with its two swap levels and one plane (profiles/rowsum_dpp_lds.md); SPD(5 .. 9) keep
+  // that form: their planes would be 15 - 45 entries a row, and nothing measured asks for it.
+  constexpr bool kGroupSums = D <= 4;
+  constexpr int RP = kGroupSums ? 4 : 1;
+  __shared__ T redM[NW][RP][TI][NP];
   __shared__ T colS[NW][NC][D * D][64];
   MM_SPD_STAMP_BEGIN();
   // (first thing: a wavefront starts at priority 0, and with the older workgroups of its CU in their row loops at 3 the prologue
@@ -555,7 +561,8 @@ __global__ __launch_bounds__((64 * bwd_waves<T, D>()), (bwd_min_waves_nc<T, D, N
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform -> row operands stay scalar loads
   bool red_writer;
-  const int red_slot = reduce_slot<NP>(lane, red_writer);  // which entry of M this lane holds after the row reduction
+  // which entry of M this lane holds after the row reduction
+  const int red_slot = kGroupSums ? group_reduce_slot<NP>(lane, red_writer) : reduce_slot<NP>(lane, red_writer);
   const int64_t base = pair_off(n, row_begin);
   MM_SPD_STAMP_MARK(0);
   // Vector issue is arbitrated oldest wavefront first: of equal shares started together, the oldest workgroup of a
@@ -575,11 +582,11 @@ __global__ __launch_bounds__((64 * bwd_waves<T, D>()), (bwd_min_waves_nc<T, D, N
   const int prio_stretch = max(wave_rows - prio_last, 3) / 3;
   int rows_left = prio_stretch;   // rows until the next priority step
   int phase = 0;   // (the row loop starts at the prologue's priority, 3)
-  // The row reduction leaves one total per lane; NP of the lanes hold distinct entries, the others duplicates.  All
-  // lanes store (an exec-masked store costs two scalar instructions per row): writers into redM, advancing by one row
-  // per row, the others into a slot of their own that does not move.
+  // The row reduction leaves one total per lane; NP of the lanes (of every lane group) hold distinct entries, the others
+  // duplicates.  All lanes store (an exec-masked store costs two scalar instructions per row): writers into redM (their
+  // group's plane), advancing by one row per row, the others into a slot of their own that does not move.
   __shared__ T redJunk[NW][64];
-  T* red_ptr = red_writer ? &redM[wave][0][red_slot] : &redJunk[wave][lane];
+  T* red_ptr = red_writer ? &redM[wave][kGroupSums ? lane >> 4 : 0][0][red_slot] : &redJunk[wave][lane];
   const int red_step = red_writer ? NP : 0;
 
   while (rem > 0) {   // one pass per column block of this workgroup's share
@@ -868,14 +875,16 @@ __global__ __launch_bounds__((64 * bwd_waves<T, D>()), (bwd_min_waves_nc<T, D, N
             ms[k] = m[0][k];
             static_for<NC - 1>([&](auto qc) { ms[k] += m[decltype(qc)::value + 1][k]; });
           }
-          *red_ptr = wave_reduce_transposed<NP, T>(ms, lane);
+          if constexpr (kGroupSums) *red_ptr = group_reduce_transposed<NP, T>(ms, lane);
+          else *red_ptr = wave_reduce_transposed<NP, T>(ms, lane);
           } else {
           static_for<NC - 1>([&](auto qc) {
             constexpr int q = decltype(qc)::value + 1;
 #pragma unroll
             for (int k = 0; k < NP; ++k) m[0][k] += m[q][k];
           });
-          *red_ptr = wave_reduce_transposed<NP, T>(m[0], lane);
+          if constexpr (kGroupSums) *red_ptr = group_reduce_transposed<NP, T>(m[0], lane);
+          else *red_ptr = wave_reduce_transposed<NP, T>(m[0], lane);
           }
           red_ptr += red_step;
          }
@@ -887,7 +896,10 @@ __global__ __launch_bounds__((64 * bwd_waves<T, D>()), (bwd_min_waves_nc<T, D, N
         for (int t = lane; t < sw * NP; t += 64) {
           const int k = t / sw, il = t - k * sw;
           const int node = SUB ? batch_node(idx32, size_t(s0 + il), n_total) : s0 + il;
-          atomic_add(&accM[size_t(k) * ns + node], redM[wave][il][k]);
+          T tot = redM[wave][0][il][k];
+#pragma unroll
+          for (int p = 1; p < RP; ++p) tot += redM[wave][p][il][k];
+          atomic_add(&accM[size_t(k) * ns + node], tot);
         }
         __builtin_amdgcn_wave_barrier();   // redM is rewritten by the next segment
         }
